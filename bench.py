@@ -17,9 +17,14 @@ every other line names its own quantity (env id, batch, GPUs) there.
 
 Rank 0 prints ONE JSON line with the contract fields plus
   "roofline":     HBM roofline of the dominant kernel, from HIP-event durations of launches of the timed region,
-  "cpu_baseline": the fp64 oracle (a CPU port of the same step, oracle/) timed on this host's cores on a bounded
-                  sample of the SAME workload: the GPU leg's settled states, xi and action sequence, auto-reset
+  "cpu_baseline": (--full only) the fp64 oracle (a CPU port of the same step, oracle/) timed on this host's cores on a
+                  bounded sample of the SAME workload: the GPU leg's settled states, xi and action sequence, auto-reset
                   included (N=1, rank 0 only).
+
+A plain run sets up, settles, warms up, times --steps steps and prints the line.  `--full` adds what takes time of its
+own: the CPU baseline, and (short timed regions) 128 more launches of the same workload, every one bracketed by HIP
+events, after the timed region so the roofline's kernel average does not rest on a handful of samples.
+`--dump-outputs DIR` writes what the last timed step returned (obs, reward, done) to DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -175,6 +180,28 @@ def cpu_baseline_cartpole(env_id, q, v, xi, acts, min_seconds=3.0):
                        "%d resets, fp64, 1 thread, %.1f s" % (env_id, n, steps, resets, dt))
 
 
+DUMP_CAP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: the arrays the last timed step returned (SoA, the env axis last, as step_soa / replay_soa return them) as
+    DIR/<name>.npy in float32 (done as 0 / 1).  Past `cap` bytes in all, the same seeded sample of envs is kept from every array
+    and its indices go to env_index.npy (float64).  Returns the names written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(a), dtype=np.float32) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[-1]
+    per_env = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    budget = cap - 4096 * (len(arrays) + 1)          # room for the .npy headers
+    if per_env * n > budget:
+        idx = np.sort(np.random.RandomState(seed).choice(n, budget // (per_env + 8), replace=False))
+        arrays = {k: np.ascontiguousarray(a[..., idx]) for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def source_digest():
     """sha256 over the kernel sources: ties a committed PMC traffic figure to the code it was measured on."""
     import hashlib
@@ -277,6 +304,12 @@ def main():
     ap.add_argument("--pin-shape", action="store_true",
                     help="strong scaling: every shard runs the launch shape the GLOBAL batch gets on one GPU (sharding.pin_global_shape), so the "
                          "sharded run reproduces the single-GPU trajectories bit for bit; default: each shard runs the fastest shape for its own size")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline and, after a short timed region, 128 "
+                         "launches with every one bracketed by HIP events for the roofline's kernel average")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done; rank 0's shard) to DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a seeded sample of envs past that)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -335,10 +368,10 @@ def main():
         cands_soa = cands.transpose(1, 2).contiguous()      # [nact, task_dim, B]
 
         def one_step(k):                                    # ONE launch: caller's SoA (state, xi, action) in, (obs', r, done) out
-            env.replay_soa(q_soa, v_soa, cands_soa[k % nact], actions[0])
+            return env.replay_soa(q_soa, v_soa, cands_soa[k % nact], actions[0])
     else:
         def one_step(k):
-            env.step_soa(actions[k % nact])
+            return env.step_soa(actions[k % nact])
 
     def sync():
         sharding.barrier()
@@ -359,7 +392,7 @@ def main():
         one_step(k)
     sync()
     env.read_timing()                                        # drop the warm-up samples
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.replay
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.replay
     if want_cpu:                                             # the CPU leg starts from exactly these states
         qs, vs = env.get_state(); xs = env.get_task()
         settled = [z.clone() for z in (qs, vs, xs)]
@@ -367,15 +400,17 @@ def main():
     sync()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        one_step(k)
+        last = one_step(k)
         counter.add(B)                                       # async all-reduce every --counter-every steps (N > 1)
     sync()
     elapsed = time.perf_counter() - t0
     kernel_ms = env.read_timing()
-    # a short timed region leaves few bracketed launches (the driver's command: 20 steps -> 4): continue the SAME workload
-    # outside the timed region with every launch bracketed, so the kernel average does not rest on a handful of samples
+    if args.dump_outputs and rank == 0:                      # before anything below steps the env again
+        dump_outputs(args.dump_outputs, {name: z.cpu().numpy() for name, z in zip(("obs", "reward", "done"), last)})
+    # a short timed region leaves few bracketed launches (the driver's command: 20 steps -> 4): with --full, continue the SAME
+    # workload outside the timed region with every launch bracketed, so the kernel average does not rest on a handful of samples
     n_extra = 0
-    if every and len(kernel_ms) < 64:
+    if args.full and every and len(kernel_ms) < 64:
         import numpy as np
         env.enable_timing(1)
         n_extra = 128

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of tuning builds on the GPU box: profiles/ab_bench.sh <lib.so> [ENV=VAL ...] -> one line per run (kernel avg ms, wall ms/step)
 LIB=$1; shift
-env REX_LIB=$LIB "$@" python bench.py --steps 400 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
+env REX_LIB=$LIB "$@" python bench.py --full --steps 400 --warmup 50 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # profiles/ab_env.sh <env-id> [ENV=VAL ...]: bench one env id with the product library (400 timed steps)
 E=$1; shift
-env "$@" python bench.py --env $E --steps 400 --warmup 100 --no-cpu-baseline 2>/dev/null | python -c "
+env "$@" python bench.py --full --env $E --steps 400 --warmup 100 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

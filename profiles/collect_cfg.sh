@@ -10,7 +10,7 @@ TAG=$1; shift
 P=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $P
-python3 bench.py "$@" > $P/bench.json 2> $P/bench.err
+python3 bench.py "$@" --full > $P/bench.json 2> $P/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- python3 bench.py "$@" --no-cpu-baseline > $P/bench_trace.log 2>&1
 SHORT="--steps 40 --warmup 10 --no-cpu-baseline"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/pmc_fetch -- python3 bench.py "$@" $SHORT > $P/bench_pmc_fetch.log 2>&1

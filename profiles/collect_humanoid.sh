@@ -8,7 +8,7 @@ P=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $P
 ARGS="--env RandomHumanoid-v0 --steps 300 --warmup 60"
-python3 bench.py $ARGS > $P/bench.log 2>&1
+python3 bench.py $ARGS --full > $P/bench.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- python3 bench.py $ARGS --no-cpu-baseline > $P/bench_trace.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM GRBM_GUI_ACTIVE --output-format csv -d $P/pmc_sq -- python3 bench.py --env RandomHumanoid-v0 --steps 40 --warmup 60 --no-cpu-baseline > $P/bench_pmc_sq.log 2>&1
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM SQ_WAVE_CYCLES --output-format csv -d $P/pmc_sq2 -- python3 bench.py --env RandomHumanoid-v0 --steps 40 --warmup 60 --no-cpu-baseline > $P/bench_pmc_sq2.log 2>&1 || true

@@ -54,3 +54,27 @@ def test_pmc_traffic_only_for_the_sources_batch_and_kernel_it_was_measured_on(tm
     assert bench.pmc_traffic("C2", 4096, "K") == (None, True)                     # the kernels changed: stale, never reported
     os.remove(root / "profiles" / "hbm_traffic.json")
     assert bench.pmc_traffic("C2", 4096, "K") == (None, False)
+
+
+def test_dump_outputs_writes_float_arrays_under_the_cap(tmp_path):
+    import numpy as np
+    rng = np.random.RandomState(3)
+    obs = rng.randn(11, 1000).astype(np.float32)
+    rew = rng.randn(1000).astype(np.float32)
+    done = (rng.rand(1000) < 0.1).astype(np.uint8)
+    assert bench.dump_outputs(str(tmp_path / "all"), dict(obs=obs, reward=rew, done=done)) == ["done", "obs", "reward"]
+    for name, ref in (("obs", obs), ("reward", rew), ("done", done)):
+        a = np.load(tmp_path / "all" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, ref.astype(np.float32))
+    # past the cap: one seeded sample of envs, the same columns of every array, the indices beside them
+    cap = 4096 * 4 + 13 * 4 * 400
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), dict(obs=obs, reward=rew, done=done), cap=cap) == ["done", "env_index", "obs", "reward"]
+    files = [tmp_path / "s1" / (n + ".npy") for n in ("obs", "reward", "done", "env_index")]
+    assert sum(os.path.getsize(f) for f in files) <= cap
+    idx = np.load(files[3])
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s2" / "env_index.npy"))
+    i = idx.astype(np.int64)
+    assert 0 < len(i) < 1000 and np.all(np.diff(i) > 0)
+    assert np.array_equal(np.load(files[0]), obs[:, i]) and np.array_equal(np.load(files[1]), rew[i])
+    assert np.array_equal(np.load(files[2]), done[i].astype(np.float32))

@@ -21,7 +21,7 @@ def _run(*extra, launcher=()):
 
 def test_headline_line_contract():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
-    d = _run("--steps", "60", "--warmup", "10", "--batch", "4096", "--cpu-sample-steps", "2")
+    d = _run("--full", "--steps", "60", "--warmup", "10", "--batch", "4096", "--cpu-sample-steps", "2")
     # (a 4 096-env line names its own quantity; BASELINE.json's string is asserted on the 32 768-env line below)
     assert d["metric"] == "env-steps/sec at batch 4096, RandomHopper-v0, 1 MI355X; % HBM roofline" and d["unit"] == "env-steps/s"
     assert base["metric"].startswith("env-steps/sec at batch 32768, RandomHopper-v0")
@@ -70,9 +70,10 @@ def test_humanoid_line():
 
 def test_driver_command_reports_the_steady_state():
     """`bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command) against a 400-step run: no one-time cost inside the
-    timed region (round 1 paid ~80 ms of first-use event set-up there: 4.1 ms per step instead of 0.14)."""
-    short = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline")
-    long_ = _run("--gpus", "1", "--steps", "400", "--warmup", "50", "--no-cpu-baseline")
+    timed region (round 1 paid ~80 ms of first-use event set-up there: 4.1 ms per step instead of 0.14).  --full: the roofline's kernel
+    average rests on the extra bracketed launches after a short timed region."""
+    short = _run("--full", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline")
+    long_ = _run("--full", "--gpus", "1", "--steps", "400", "--warmup", "50", "--no-cpu-baseline")
     assert short["config"]["global_batch"] == 32768
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert short["metric"] == base["metric"] and long_["metric"] == base["metric"]   # the north-star line carries BASELINE.json's metric verbatim
@@ -85,6 +86,32 @@ def test_driver_command_reports_the_steady_state():
         # is bracketed: the wall-clock fraction may exceed the event-based one by that much)
         assert r["frac_wall"] <= r["frac"] * 1.06 and r["kernel_launches_timed"] >= 4
         assert d["host_gap_ms"] is not None and abs(d["host_gap_ms"]) < 0.25 * d["ms_per_step"] * d["steps"]
+
+
+def test_plain_run_is_lean_and_dumps_what_its_last_step_returned(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times N steps and measures nothing else (no CPU baseline, no launches after the
+    timed region); --dump-outputs writes what the last timed step returned, the same from run to run and under --full."""
+    import numpy as np
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    runs = [("--gpus", "1", "--steps", "20", "--warmup", "5"), ("--gpus", "1", "--steps", "20", "--warmup", "5"),
+            ("--full", "--no-cpu-baseline", "--gpus", "1", "--steps", "20", "--warmup", "5")]
+    lines = [_run(*a, "--dump-outputs", str(tmp_path / str(i))) for i, a in enumerate(runs)]
+    d = lines[0]
+    assert d["metric"] == base["metric"] and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 20 and d["warmup"] == 5 and "cpu_baseline" not in d
+    assert abs(d["value"] - 32768 * 20 / (d["ms_per_step"] * 20 / 1e3)) < 1e-6 * d["value"]
+    r = d["roofline"]
+    assert r["kernel_launches_timed"] == r["kernel_launches_timed_in_region"] >= 1 and r["kernel_avg_ms"] == r["kernel_avg_ms_in_region"]
+    assert lines[2]["roofline"]["kernel_launches_timed"] > lines[2]["roofline"]["kernel_launches_timed_in_region"]
+    out = [{n: np.load(tmp_path / str(i) / (n + ".npy")) for n in ("obs", "reward", "done")} for i in range(3)]
+    assert sorted(os.listdir(tmp_path / "0")) == ["done.npy", "obs.npy", "reward.npy"]
+    o = out[0]
+    assert o["obs"].shape == (11, 32768) and o["reward"].shape == (32768,) and o["done"].shape == (32768,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in o.values())
+    assert set(np.unique(o["done"])) <= {0.0, 1.0} and np.abs(o["reward"]).max() > 0
+    for other in out[1:]:
+        for n in o:
+            assert np.array_equal(o[n], other[n]), n
 
 
 def test_two_rank_rehearsal_on_one_gpu():

@@ -242,7 +242,7 @@ def test_bench_config_lines(cfg, eid, B, kernel, nbytes):
     """`bench.py --config C1..C5`: SURVEY 8(d)'s inputs, each line with the roofline of its own kernel, a `metric` that names what the
     line measured (BASELINE.json's string belongs to the north-star line alone) and (C1, C2) the CPU leg on the GPU leg's settled states."""
     extra = () if cfg in ("C1", "C2") else ("--no-cpu-baseline",)
-    d = _bench("--config", cfg, "--steps", "24", "--warmup", "4", "--settle", "60", "--cpu-sample-steps", "2", *extra)
+    d = _bench("--full", "--config", cfg, "--steps", "24", "--warmup", "4", "--settle", "60", "--cpu-sample-steps", "2", *extra)
     assert d["metric"] == "env-steps/sec at batch %d, %s, 1 MI355X; %% HBM roofline" % (B, eid)
     assert d["metric"] != json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
     w = d["config"]["workload"]
