@@ -190,8 +190,10 @@ int rex_get_counters(rex_t* h, int64_t* out);
 int rex_get_launch_shape(const rex_t* h, int32_t* out);
 /* Pins the launch shape of a handle (same four int32 as rex_get_launch_shape, [host]; -1 keeps a field): every shape runs the same solver to
  * the same minimiser, but which solver instantiation a wave enters depends on the shape, so two runs agree bit for bit only under the same
- * shape.  sharding.shard_strong pins every shard to the shape the GLOBAL batch would get on one GPU, which makes an index-sharded run reproduce the
- * single-GPU trajectories exactly.  Pure host bookkeeping (the shape is read at launch time); REX_ERR_ARG for a shape the env kind has no kernel
+ * shape.  Unpinned is the default: every handle runs the shape rex_create picked for its own batch.  sharding.pin_global_shape (opt-in; shard_strong
+ * only places the shard boundaries) pins a shard to the shape the GLOBAL batch would get on one GPU, which makes an index-sharded run reproduce the
+ * single-GPU trajectories exactly.  The walker2d auto-reset under DR derives the new geometry inside the step kernel below 524 288 envs per GPU and
+ * in a launch of its own from there; that choice is not part of the shape and the two give the same bits.  Pure host bookkeeping (the shape is read at launch time); REX_ERR_ARG for a shape the env kind has no kernel
  * for.  No reference counterpart. */
 int rex_set_launch_shape(rex_t* h, const int32_t* shape);
 

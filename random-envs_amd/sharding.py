@@ -47,9 +47,12 @@ def shape_for_batch(kind, batch, simds=1024):
 def pin_global_shape(env, global_batch, simds=None):
     """Give a shard the launch shape its GLOBAL batch would get on one GPU (rex_set_launch_shape).  rex_create picks the shape from
     the per-GPU batch: 65 536 envs on one GPU run one lane per env, the same envs split over two GPUs two lanes per env, and the two
-    kernels round differently.  Pinned, an index-sharded run reproduces the single-GPU trajectories bit for bit (given shard
-    boundaries on whole waves: shard_strong); unpinned, every shard runs the fastest shape for its own size and agrees with the
-    single-GPU run to fp32 rounding only."""
+    kernels round differently; a walker2d / half-cheetah batch of 16 384 envs runs 32-lane pair blocks, an 8 192-env shard 16.
+    Pinned, an index-sharded run reproduces the single-GPU trajectories bit for bit (given shard boundaries on whole waves:
+    shard_strong), auto-resets under DR included: the walker2d geometry derivation, in the step kernel below 524 288 envs per GPU
+    and in a launch of its own from there, gives the same bits either way, so it needs no pinning
+    (tests/test_gpu_launch_shapes.py::test_pinned_shard_reproduces_the_single_gpu_run).  Pinning is opt-in: unpinned, every shard
+    runs the fastest shape for its own size and agrees with the single-GPU run to fp32 rounding only."""
     if simds is None:
         import torch
         simds = 4 * torch.cuda.get_device_properties(env.device).multi_processor_count
@@ -68,7 +71,7 @@ def shard_strong(global_batch, rank, world, align=WAVE_ENVS):
     as in the single-GPU run.  Everything the RNG decides is bit-identical under any split.  The ARITHMETIC of a lane also depends
     on which solver instantiation its wave picks and on the launch shape rex_create derives from the PER-GPU batch, so an
     index-sharded run reproduces the single-GPU trajectories bit for bit only when the shards also run the global batch's shape
-    (`pin_global_shape`, `bench.py --pin-shape`) or under REX_FAST=0; otherwise lanes agree to fp32 rounding.  The remainder goes to
+    (`pin_global_shape`, `bench.py --pin-shape`: this function does not pin) or under REX_FAST=0; otherwise lanes agree to fp32 rounding.  The remainder goes to
     the low ranks, the last rank takes what is left."""
     align = max(int(align), 1)
     blocks, tail = divmod(global_batch, align)
