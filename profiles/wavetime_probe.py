@@ -29,6 +29,21 @@ for eid in sys.argv[1:] or ["RandomHopper-v0"]:
         print("   last launch, cycles per wave [mean / max]: load state %.0f / %.0f | substeps %.0f / %.0f | reward, obs, stores %.0f / %.0f | fused reset %.0f / %.0f | "
               "sum of means %.0f, slowest wave %.0f; kernel %.4f ms" % (P[:, 0].mean(), P[:, 0].max(), P[:, 1].mean(), P[:, 1].max(), P[:, 2].mean(), P[:, 2].max(),
                                                                      P[:, 3].mean(), P[:, 3].max(), P.sum(1).mean(), P.sum(1).max(), ms))
+    if hasattr(_native.lib(), "rex_debug_wavetail") and "Humanoid" not in eid:
+        # the tail of a wave (everything behind the substeps) split by stamps; one launch, the accessor zeroes what the reset path accumulates
+        tl = (ctypes.c_ulonglong * (1024 * 8))(); _native.lib().rex_debug_wavetail(tl, 1024)
+        env.step_soa(acts[1]); torch.cuda.synchronize()
+        _native.lib().rex_debug_wavephase(ph, 1024); _native.lib().rex_debug_wavetail(tl, 1024)
+        P = np.array(list(ph), dtype=np.float64).reshape(1024, 4); T = np.array(list(tl), dtype=np.float64).reshape(1024, 8)
+        rs = T[:, 5] > 0                                          # waves that ran the reset
+        seg = [("t returned", T[:, 0]), ("reward logic, stepped stores issued", T[:, 1] - T[:, 0])]
+        if rs.any():
+            R = T[rs]
+            seg += [("episode returned", R[:, 2]), ("state draws + stores", R[:, 3] - R[:, 2]), ("xi draws + stores", R[:, 4] - R[:, 3]),
+                    ("rest of the reset (walker2d: re-derive)", R[:, 5] - R[:, 4])]
+        print("   tail of one launch, cycles per wave [mean / max] (%d of %d waves ran the reset; reset rows over those): " % (rs.sum(), len(rs)) +
+              " | ".join("%s %.0f / %.0f" % (nm, x.mean(), x.max()) for nm, x in seg) +
+              " | whole tail (load state + epilogue + reset) %.0f / %.0f" % ((P[:, 0] + P[:, 2] + P[:, 3]).mean(), (P[:, 0] + P[:, 2] + P[:, 3]).max()))
     if hasattr(_native.lib(), "rex_debug_evalphase") and "Humanoid" not in eid:
         ep = (ctypes.c_ulonglong * (1024 * 16))(); _native.lib().rex_debug_evalphase(ep, 1024)   # 16 slots per wave
         for k in range(10): env.step_soa(acts[k % 8])

@@ -57,6 +57,7 @@ extern "C" int rex_debug_ktime(unsigned long long* out) {   // diagnostic build 
 // B = 32 768 is the SLOWEST wave's, not the average)
 namespace rex { __device__ unsigned long long g_wavetime[8192]; __device__ unsigned long long g_waveinfo[8192][8]; __device__ unsigned long long g_wavehum[1024][16];
                 __device__ unsigned long long g_wavephase[8192][4];
+                __device__ unsigned long long g_wavetail[8192][8];    // planar step kernel: what the tail of a wave (everything behind the substeps) spends where
                 __device__ unsigned long long g_waveplace[8192][4];   // 100 MHz clock at entry and exit, HW_ID, XCC_ID: where and when each wave ran
                 }
 #endif
@@ -70,6 +71,12 @@ extern "C" int rex_debug_evalphase(unsigned long long* out, int n) {
 // g_wavephase: planar step kernel, cycles entry -> state loaded -> substeps done -> outputs stored -> fused reset done
 extern "C" int rex_debug_wavephase(unsigned long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavephase), sizeof(unsigned long long) * 4 * (n < 8192 ? n : 8192)) == hipSuccess ? 0 : -1; }
+// g_wavetail: cycles from the end of the substeps to [0] t and episode back from LDS, [1] reward / done / info stores issued; from there to [2] episode stored,
+// [3] reset state and observation drawn, [4] xi draws done and stored, [5] end of the reset path (walker2d: the re-derive); the one set of
+// state / obs stores follows.  [2..5] are maxima over the launches since the last read (zeroed here) and stay 0 for a wave that skipped the reset.
+extern "C" int rex_debug_wavetail(unsigned long long* out, int n) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavetail), sizeof(unsigned long long) * 8 * (n < 8192 ? n : 8192)) != hipSuccess) return -1;
+  static unsigned long long z[8192][8]; return hipMemcpyToSymbol(HIP_SYMBOL(rex::g_wavetail), z, sizeof z) == hipSuccess ? 0 : -1; }
 extern "C" int rex_debug_waveplace(unsigned long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_waveplace), sizeof(unsigned long long) * 4 * (n < 8192 ? n : 8192)) == hipSuccess ? 0 : -1; }
 extern "C" int rex_debug_wavehum(unsigned long long* out) {   // humanoid: per-wave phase accumulators of the last launch (-DREX_KTIME -DREX_WAVETIME)
@@ -157,39 +164,112 @@ __device__ __forceinline__ float truncnorm2(float u) {
 
 // RandomEnv.sample_task (random_env.py:148-203), one lane = one env.  Cold path (reset only): runtime dimension,
 // rolled loops, every draw stored straight to its xi row (no per-lane array => the kernel needs no scratch).
+// RNG: where the draws come from -- rocRAND's engine (EngineRng: the reset kernels, rex_sample_task) or the same word stream held in
+// registers (PhiloxWords, below: the planar step kernel's fused reset).
+struct EngineRng {
+  rocrand_state_philox4x32_10 st;
+  __device__ __forceinline__ EngineRng(unsigned long long seed, unsigned long long subseq, unsigned long long offset) { rocrand_init(seed, subseq, offset, &st); }
+  __device__ __forceinline__ float uniform() { return rocrand_uniform(&st); }
+  __device__ __forceinline__ float normal() { return rocrand_normal(&st); }
+};
+template <class RNG = EngineRng>
 __device__ void sample_task(const DRParams& dr, unsigned long long seed, unsigned long long subseq, unsigned long long offset,
                             float* __restrict__ xi_rows, size_t B, unsigned i, unsigned long long* counters) {
   const int d = dr.dim;
-  rocrand_state_philox4x32_10 st;
-  rocrand_init(seed, subseq, offset, &st);
+  RNG st(seed, subseq, offset);
   if (dr.type == REX_DR_UNIFORM) {           // :150-151  U(min, max) per dim
-    for (int k = 0; k < d; k++) { float u = rocrand_uniform(&st); (xi_rows + (size_t)dr.map[k] * B)[i] = dr.a[k] + (dr.b[k] - dr.a[k]) * (1.0f - u); }
+    for (int k = 0; k < d; k++) { float u = st.uniform(); (xi_rows + (size_t)dr.map[k] * B)[i] = dr.a[k] + (dr.b[k] - dr.a[k]) * (1.0f - u); }
   } else if (dr.type == REX_DR_TRUNCNORM) {  // :153-171 (intended semantics; the reference raises NameError)
     for (int k = 0; k < d; k++) {
       float lb = dr.lower[k];
-      float obs = dr.a[k] + dr.b[k] * truncnorm2(rocrand_uniform(&st));
+      float obs = dr.a[k] + dr.b[k] * truncnorm2(st.uniform());
       // `attempts` 1,2 keep a redraw; the third redraw is overwritten by lower_bound (:162-167)
-      for (int att = 0; att < 2 && obs < lb; att++) obs = dr.a[k] + dr.b[k] * truncnorm2(rocrand_uniform(&st));
+      for (int att = 0; att < 2 && obs < lb; att++) obs = dr.a[k] + dr.b[k] * truncnorm2(st.uniform());
       if (obs < lb) obs = lb;
       (xi_rows + (size_t)dr.map[k] * B)[i] = obs;
     }
   } else if (dr.type == REX_DR_GAUSSIAN) {   // :173-190: redraw while < 0.1, raise after the 3rd failure
     for (int k = 0; k < d; k++) {
-      float obs = dr.a[k] + dr.b[k] * rocrand_normal(&st);
-      for (int att = 0; att < 2 && obs < 0.1f; att++) obs = dr.a[k] + dr.b[k] * rocrand_normal(&st);
+      float obs = dr.a[k] + dr.b[k] * st.normal();
+      for (int att = 0; att < 2 && obs < 0.1f; att++) obs = dr.a[k] + dr.b[k] * st.normal();
       if (obs < 0.1f) { obs = 0.1f; atomicAdd(counters + 1, 1ull); }   // a device lane cannot raise: clamp + count
       (xi_rows + (size_t)dr.map[k] * B)[i] = obs;
     }
   } else if (dr.type == REX_DR_FULLGAUSSIAN) {  // :192-198: MVN in normalised [0,4]^d, clip, denormalise (:205-220)
     // x_k = mean_k + sum_{j<=k} L_kj z_j: the z stream is replayed from the counter for every k (no z[] array)
     for (int k = 0; k < d; k++) {
-      rocrand_state_philox4x32_10 sz; rocrand_init(seed, subseq, offset, &sz);
+      RNG sz(seed, subseq, offset);
       float acc = dr.a[k];
-      for (int j = 0; j <= k; j++) acc += dr.chol[k * MAX_XI + j] * rocrand_normal(&sz);
+      for (int j = 0; j <= k; j++) acc += dr.chol[k * MAX_XI + j] * sz.normal();
       acc = fminf(fmaxf(acc, 0.0f), 4.0f);
       (xi_rows + (size_t)dr.map[k] * B)[i] = acc * (dr.hi[k] - dr.lo[k]) * 0.25f + dr.lo[k];
     }
   }
+}
+
+// ---- counter-based Philox4x32-10 in registers (the planar step kernel's fused reset and observation noise) ----
+// The streams are stateless by design (subsequence = global env index, offset = f(episode, t), every region starts on a multiple of 4), so a
+// consumer that knows at compile time which words it needs has no use for the engine's state (four result words indexed by a runtime
+// `substate`, a look-ahead block on every 4th draw, a per-draw "block exhausted?" branch).  philox_block gives the four words the engine
+// returns for draws 4 b .. 4 b + 3 of rocrand_init(seed, subsequence, offset), `block` = offset / 4 + b: rocrand_philox4x32_10.h forms the
+// counter as (offset / 4 in .xy, subsequence in .zw) and the key from the seed (restart, discard_subsequence_impl, discard_impl), ten rounds.
+__device__ __forceinline__ void philox_block(unsigned long long seed, unsigned long long subseq, unsigned long long block, unsigned* __restrict__ w) {
+  unsigned c0 = (unsigned)block, c1 = (unsigned)(block >> 32), c2 = (unsigned)subseq, c3 = (unsigned)(subseq >> 32);
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// NBLK consecutive blocks from `block0` into w[4 NBLK]; the blocks are independent, the compiler interleaves their rounds
+template <int NBLK>
+__device__ __forceinline__ void philox_blocks(unsigned long long seed, unsigned long long subseq, unsigned long long block0, unsigned (&w)[4 * NBLK]) {
+  static_for<0, NBLK>([&](auto BB) { constexpr int b = BB; philox_block(seed, subseq, block0 + (unsigned long long)b, w + 4 * b); });
+}
+// the conversions rocrand_uniform / rocrand_normal apply to the engine's words
+__device__ __forceinline__ float philox_uniform(unsigned w) { return rocrand_device::detail::uniform_distribution(w); }
+__device__ __forceinline__ float2 philox_normal2(unsigned w0, unsigned w1) { return rocrand_device::detail::normal_distribution2(w0, w1); }
+
+// The engine's draw sequence for consumers whose number of draws depends on the data (truncnorm / gaussian redraws): word j of the stream is
+// draw j, a block is evaluated when its first word is asked for (no look-ahead), the four words sit in registers and are picked by
+// selects, rocrand_normal's Box-Muller pairing (two words -> .x now, .y at the next call) is kept.  Offsets are multiples of 4.
+struct PhiloxWords {
+  unsigned long long seed, subseq, block; unsigned w[4]; int n; float saved; bool has;
+  __device__ __forceinline__ PhiloxWords(unsigned long long seed_, unsigned long long subseq_, unsigned long long offset)
+      : seed(seed_), subseq(subseq_), block(offset >> 2), n(4), saved(0.0f), has(false) {}
+  __device__ __forceinline__ unsigned next() {
+    if (n == 4) { philox_block(seed, subseq, block, w); block++; n = 0; }
+    const unsigned r = n == 0 ? w[0] : n == 1 ? w[1] : n == 2 ? w[2] : w[3];
+    n++;
+    return r;
+  }
+  __device__ __forceinline__ float uniform() { return philox_uniform(next()); }
+  __device__ __forceinline__ float normal() {
+    if (has) { has = false; return saved; }
+    const unsigned a = next(), b = next();
+    const float2 r = philox_normal2(a, b);
+    saved = r.y; has = true;
+    return r.x;
+  }
+};
+
+// sample_task's REX_DR_UNIFORM case for a compile-time bound on the dimension: draw k is word k of the stream, the parameters are fetched
+// in one batch before the draws and no store address waits on a scalar load of its own.  Same values, same stores.
+template <int NXI>
+__device__ __forceinline__ void sample_task_uniform(const DRParams& dr, unsigned long long seed, unsigned long long subseq, unsigned long long offset,
+                                                    float* __restrict__ xi_rows, size_t B, unsigned i) {
+  const int d = dr.dim;
+  float a[NXI], b[NXI]; int m[NXI];
+  static_for<0, NXI>([&](auto KK) { constexpr int k = KK; a[k] = dr.a[k]; b[k] = dr.b[k]; m[k] = dr.map[k]; });
+  constexpr int NBLK = (NXI + 3) / 4;
+  unsigned w[4 * NBLK];
+  static_for<0, NBLK>([&](auto BB) { constexpr int bb = BB; if (4 * bb < d) philox_block(seed, subseq, (offset >> 2) + (unsigned long long)bb, w + 4 * bb); });
+  static_for<0, NXI>([&](auto KK) { constexpr int k = KK;
+    if (k < d) { float u = philox_uniform(w[k]); (xi_rows + (size_t)m[k] * B)[i] = a[k] + (b[k] - a[k]) * (1.0f - u); } });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -301,6 +381,45 @@ __device__ __forceinline__ void write_obs(const float (&q)[S::NV], const float (
   });
 }
 
+// the same observation into registers; the noise of write_obs from the stream's blocks: rocrand_normal draws two words for observation 2 p
+// (Box-Muller .x) and hands the saved .y to observation 2 p + 1
+template <class S>
+__device__ __forceinline__ void obs_values(const float (&q)[S::NV], const float (&v)[S::NV], float (&ob)[S::NOBS], bool noisy, float noise_std,
+                                           unsigned long long seed, unsigned long long subseq, unsigned long long offset) {
+  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; ob[k] = k < S::NV - 1 ? q[k + 1] : v[k - (S::NV - 1)]; });
+  if (noisy) {
+    constexpr int NP = (S::NOBS + 1) / 2, NBLK = (2 * NP + 3) / 4;
+    unsigned w[4 * NBLK];
+    philox_blocks<NBLK>(seed, subseq, offset >> 2, w);
+    static_for<0, NP>([&](auto PP) { constexpr int p = PP;
+      const float2 n = philox_normal2(w[2 * p], w[2 * p + 1]);
+      ob[2 * p] += noise_std * n.x;
+      if constexpr (2 * p + 1 < S::NOBS) ob[2 * p + 1] += noise_std * n.y; });
+  }
+}
+// reset_model's state of episode `ep` (planar_reset_lane below draws the same words through the engine): word 2 k -> qpos[k], word 2 k + 1 ->
+// qvel[k]; half-cheetah: qvel is normal, a Box-Muller pair serves two velocities, so dofs 2 p and 2 p + 1 take words 4 p .. 4 p + 3 as
+// (qpos[2 p], pair, pair, qpos[2 p + 1])
+template <class S>
+__device__ __forceinline__ void reset_state_values(unsigned long long seed, unsigned long long subseq, unsigned ep, float (&q)[S::NV], float (&v)[S::NV]) {
+  constexpr int NV = S::NV;
+  constexpr int NW = S::KIND == 2 ? 4 * (NV / 2) + (NV % 2 ? 3 : 0) : 2 * NV, NBLK = (NW + 3) / 4;
+  unsigned w[4 * NBLK];
+  philox_blocks<NBLK>(seed, subseq, ((unsigned long long)ep * EP_STRIDE) >> 2, w);
+  const float c = S::INIT_NOISE;
+  if constexpr (S::KIND == 2) {
+    static_for<0, (NV + 1) / 2>([&](auto PP) { constexpr int p = PP;
+      const float2 n = philox_normal2(w[4 * p + 1], w[4 * p + 2]);                       // random_half_cheetah.py:125
+      q[2 * p] = c * (2.0f * (1.0f - philox_uniform(w[4 * p])) - 1.0f); v[2 * p] = 0.1f * n.x;
+      if constexpr (2 * p + 1 < NV) { q[2 * p + 1] = c * (2.0f * (1.0f - philox_uniform(w[4 * p + 3])) - 1.0f); v[2 * p + 1] = 0.1f * n.y; } });
+  } else {
+    static_for<0, NV>([&](auto KK) { constexpr int k = KK;
+      q[k] = c * (2.0f * (1.0f - philox_uniform(w[2 * k])) - 1.0f);                     // init_qpos + U(-c, c)
+      v[k] = c * (2.0f * (1.0f - philox_uniform(w[2 * k + 1])) - 1.0f); });
+    q[1] += 1.25f;                                                                      // init_qpos[1] = 1.25 (ref, hopper.xml:30)
+  }
+}
+
 template <class S>
 __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepFlags& fl, const DRParams& dr, int resample,
                                                   int reset_state, unsigned i, float* __restrict__ obs);
@@ -349,10 +468,16 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
   const unsigned i = (blk * blockDim.x + threadIdx.x) >> (PAIR ? 1 : 0);   // 32-bit lane offset + uniform (SGPR) row bases
   if (i >= s.B) return;   // (both lanes of a pair leave together: i is the same)
   const long long B = s.B;
+  // t and episode are wanted behind the substeps only.  Loaded there, each is a memory round trip with nothing to overlap; loaded here they
+  // share the state's.  They wait in two words of LDS, not in registers the solver would have to carry (read back through an opaque copy
+  // of the lane's index: the compiler must not forward the stored values to the loads, which would keep them in VGPRs after all).
+  __shared__ unsigned tail_park[2 * 64];
+  const int t_in = s.t[i]; const unsigned ep_in = s.episode[i];
   float q[S::NV], v[S::NV], ctrl[S::NU], xi[S::NXI];
   static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (s.qpos + (size_t)k * B)[i]; v[k] = (s.qvel + (size_t)k * B)[i]; });
   static_for<0, S::NU>([&](auto KK) { constexpr int k = KK; ctrl[k] = (action + (size_t)k * B)[i]; });
   static_for<0, S::NXI>([&](auto KK) { constexpr int k = KK; xi[k] = (s.xi + (size_t)k * B)[i]; });
+  tail_park[threadIdx.x] = (unsigned)t_in; tail_park[64 + threadIdx.x] = ep_in;
   PlanarGeom<float, S> G; load_geom<S>(s, i, ugeom, G);
   LaneParams<float, S> P; lane_params(S{}, xi, P);
   // the dynamics are invariant to the root x translation: integrate the step from x = 0 so the
@@ -411,39 +536,76 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
     if (!finite) atomicAdd(s.counters + 0, 1ull);
     if (capped && threadIdx.x == 0) atomicAdd(s.counters + 2, 1ull);
   }
-  int t = s.t[io] + 1;
+  unsigned lo = threadIdx.x; asm volatile("" : "+v"(lo));
+  const unsigned ep_prev = tail_park[64 + lo];
+  int t = (int)tail_park[lo] + 1;
+#if defined(REX_WAVETIME)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long tt0 = __builtin_amdgcn_s_memtime();
+#endif
   bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;     // gym TimeLimit
   bool d = dn || trunc;
-  if (!fl.readonly) {
-    s.t[io] = t;
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[io] = q[k]; (s.qvel + (size_t)k * B)[io] = v[k]; });
-    s.done[io] = d ? 2 : 0;
-  }
-  rocrand_state_philox4x32_10 st;
-  if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + io),
-                             (unsigned long long)s.episode[io] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, &st);
-  write_obs<S>(q, v, obs, B, io, fl.noisy != 0, fl.noise_std, &st);
-  if (term_obs) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (term_obs + (size_t)k * B)[io] = (obs + (size_t)k * B)[io]; });
+  const unsigned long long subseq = (unsigned long long)(s.env_offset + io);
+  float ob[S::NOBS];
+  obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq,
+                (unsigned long long)ep_prev * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE);
+  // what always carries the STEPPED values goes out first
+  if (term_obs) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (term_obs + (size_t)k * B)[io] = ob[k]; });
   reward[io] = r; done_out[io] = d ? 1 : 0;
   if (trunc_out) trunc_out[io] = trunc ? 1 : 0;
   if (fl.info) { fl.info[io] = dx / dt; (fl.info + (size_t)B)[io] = -S::CTRL_COST * asq; }   // info: reward_run, reward_ctrl (random_half_cheetah.py:105-110)
-  // auto-reset fused into the step launch: finished lanes restart here (saves the masked reset launch and
-  // the kernel boundary, ~10 % of a hopper step at B = 32768)
 #if defined(REX_WAVETIME)
   const unsigned long long tr0 = __builtin_amdgcn_s_memtime();
 #endif
+  // Auto-reset fused into the step launch (saves the masked reset launch and the kernel boundary).  A finished lane's state, t, done and
+  // observation are REPLACED in registers by those of its next episode before anything is stored: every row is written once, by one
+  // set of stores for the whole wave, and nothing in the tail waits for memory (t and episode came with the state; gfx950 counts loads
+  // and stores in one counter, so a load waited for here would drain every store issued before it).
+  unsigned char dflag = d ? 2 : 0;
   if (fused_reset && d) {
-    planar_reset_lane<S>(s, fl, dr, resample & RS_RESAMPLE, 1, io, obs);
-    if constexpr (S::KIND == 3) {
+    const unsigned ep = ep_prev + 1; s.episode[io] = ep;
+#if defined(REX_WAVETIME)
+    atomicMax(&g_wavetail[blockIdx.x & 8191][2], __builtin_amdgcn_s_memtime() - tr0);
+#endif
+#if defined(REX_DIAG_CHEAP_RESET)   // timing diagnostics only: what the RNG work of the fused reset costs the step kernel
+    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (k == 1 && S::KIND != 2) ? 1.25f : 0.0f; v[k] = 0.0f; });
+    t = 0; dflag = 0;
+#else
+    reset_state_values<S>(s.seed, subseq, ep, q, v);
+    t = 0; dflag = 0;
+    obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + STEP_BASE);
+#if defined(REX_WAVETIME)
+    atomicMax(&g_wavetail[blockIdx.x & 8191][3], __builtin_amdgcn_s_memtime() - tr0);
+#endif
+    if ((resample & RS_RESAMPLE) && dr.type != REX_DR_NONE) {
+      // separate stream region so the xi draw does not depend on the state draws.  truncnorm / gaussian consume a data-dependent number
+      // of words (redraw rules) and fullgaussian replays the stream per dimension: they take their words from PhiloxWords
+      if (dr.type == REX_DR_UNIFORM && dr.dim <= S::NXI) sample_task_uniform<S::NXI>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io);
+      else sample_task<PhiloxWords>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io, s.counters);
+    }
+#if defined(REX_WAVETIME)
+    atomicMax(&g_wavetail[blockIdx.x & 8191][4], __builtin_amdgcn_s_memtime() - tr0);
+#endif
+    if constexpr (S::KIND == 3) {   // (reads the new xi lengths back behind their stores)
       if (resample & RS_DERIVE) {
         if constexpr (PAIR) walker_derive_lane(s, io, (resample & RS_REFRESH) ? 1 : 0);
         else walker_derive_call(s, io, (resample & RS_REFRESH) ? 1 : 0);   // (one lane per env: inlined it spills the step's own state; as a call only this branch pays)
       }
     }
+#endif
+#if defined(REX_WAVETIME)
+    atomicMax(&g_wavetail[blockIdx.x & 8191][5], __builtin_amdgcn_s_memtime() - tr0);
+#endif
   }
+  if (!fl.readonly) {
+    s.t[io] = t;
+    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[io] = q[k]; (s.qvel + (size_t)k * B)[io] = v[k]; });
+    s.done[io] = dflag;
+  }
+  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (obs + (size_t)k * B)[io] = ob[k]; });
 #if defined(REX_WAVETIME)
   if ((threadIdx.x & 63) == 0) { g_waveinfo[blockIdx.x & 8191][1] += __builtin_amdgcn_s_memtime() - tr0; }   // slot 1 ("iters", unused): cycles in the fused reset
   if ((threadIdx.x & 63) == 0) { unsigned long long* ph = g_wavephase[blockIdx.x & 8191]; ph[0] = tk0 - tp0; ph[1] = tk1 - tk0; ph[2] = tr0 - tk1; ph[3] = __builtin_amdgcn_s_memtime() - tr0; }
+  if ((threadIdx.x & 63) == 0) { unsigned long long* tl = g_wavetail[blockIdx.x & 8191]; tl[0] = tt0 - tk1; tl[1] = tr0 - tk1; }
   if ((threadIdx.x & 63) == 0) { unsigned long long* pl = g_waveplace[blockIdx.x & 8191]; pl[0] = tw0; pl[1] = __builtin_amdgcn_s_memrealtime();
     pl[2] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4); pl[3] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20); }   // HW_REG_HW_ID, HW_REG_XCC_ID
 #endif
