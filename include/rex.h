@@ -204,6 +204,59 @@ int rex_set_launch_shape(rex_t* h, const int32_t* shape);
 int rex_enable_timing(rex_t* h, int every);   /* 0 = off, n >= 1 = bracket every n-th rex_step launch */
 int rex_read_timing(rex_t* h, float* ms_out, int max_n);
 
+/* ---- observation / reward normalisation and episode statistics: an opt-in post-pass of rex_step / rex_reset -------------------
+ * What an RL loop places directly above step(): stable-baselines3's VecNormalize (common/vec_env/vec_normalize.py) with its
+ * RunningMeanStd (common/running_mean_std.py), and VecMonitor (common/vec_env/vec_monitor.py) -- the reference's users train
+ * through SB3 (README.md:68).  No reference counterpart of its own.  rex_step, rex_reset and their outputs are untouched: the calls
+ * below READ the raw buffers rex_step wrote and write normalised values to buffers of the caller (which may be the same buffers:
+ * in place works).
+ *
+ * State: one running (count, mean, var) per observation row and one for the discounted return (obs_dim + 1 rows; initial count
+ * 1e-4, mean 0, var 1), and per lane the discounted return `ret`, the episode's raw return and its length.
+ *
+ * rex_norm_step, with training on:  (1) the observation statistics take in the batch's obs_in (Chan merge with the batch's
+ *   population moments; after an auto-reset these are the new episode's first observations, as in SB3), (2) ret = ret*gamma + reward,
+ *   (3) the return statistic takes in ret.  Always: obs_out = clip((obs_in - mean) / sqrt(var + epsilon), +-clip_obs),
+ *   reward_out = clip(reward_in / sqrt(var_ret + epsilon), +-clip_reward), term_obs_out of the lanes with done != 0 the same way as
+ *   obs_out (other lanes of term_obs_out are left as they were), and finally ret = 0 on the done lanes.
+ *   Episode statistics: ep_return += reward_in, ep_len += 1; a done lane writes its totals to ep_return_out [dev, double batch] /
+ *   ep_len_out [dev, int32 batch] (other lanes are left as they were), adds them to three device aggregates (episodes finished, sum of
+ *   returns, sum of lengths) and starts again from 0.
+ *   A switch that is off (norm_obs / norm_reward) leaves its statistic, and its output buffers, alone; with norm_reward off ret stays 0.
+ *   Optional pointers: obs_in + obs_out (together; NULL skips the observation rows), term_obs_in + term_obs_out (together), reward_out,
+ *   ep_return_out, ep_len_out.
+ * rex_norm_reset: the lanes with mask[i] != 0 (all when mask == NULL) get ret = 0 and fresh episode totals; with training on the
+ *   observation statistics take in obs_in of THOSE lanes (the batch count is their number); their normalised observations go to
+ *   obs_out (other lanes of obs_out are left as they were).
+ * A non-finite input element is left out of its row's batch moments (so the count is kept per row; all rows agree while inputs are
+ *   finite) and counted; its normalised output is whatever the arithmetic gives.
+ *
+ * Two launches per call on `stream`, no allocation, no synchronisation; results do not depend on anything but the data (fixed
+ * reduction order: two runs agree bit for bit).  rex_norm_enable is the only allocating call (it synchronises; calling it again
+ * re-initialises the state under the new config); every other rex_norm_* call before it returns REX_ERR_STATE. */
+typedef struct rex_norm_config {
+  double gamma;        /* 0.99 */
+  double epsilon;      /* 1e-8 */
+  double clip_obs;     /* 10   */
+  double clip_reward;  /* 10   */
+  int norm_obs, norm_reward, training;   /* 1, 1, 1 */
+} rex_norm_config;
+int rex_norm_enable(rex_t* h, const rex_norm_config* cfg /* NULL = the defaults above */);
+int rex_norm_set_training(rex_t* h, int flag);
+int rex_norm_reset(rex_t* h, const uint8_t* mask, const float* obs_in, float* obs_out, void* stream);
+int rex_norm_step(rex_t* h, const float* obs_in, const float* reward_in, const uint8_t* done, const float* term_obs_in,
+                  float* obs_out, float* reward_out, float* term_obs_out, double* ep_return_out, int32_t* ep_len_out, void* stream);
+/* the running statistics as [host] double[3 * (obs_dim + 1)]: the counts of every row, then the means, then the variances (the
+ * return row last in each).  Both synchronise the device. */
+int rex_norm_get_stats(rex_t* h, double* out);
+int rex_norm_set_stats(rex_t* h, const double* in);
+/* the per-lane state [dev]: ret, ep_return (double batch), ep_len (int32 batch); with the statistics it makes a resume exact. */
+int rex_norm_get_lane_state(rex_t* h, double* ret, double* ep_return, int32_t* ep_len, void* stream);
+int rex_norm_set_lane_state(rex_t* h, const double* ret, const double* ep_return, const int32_t* ep_len, void* stream);
+/* out [host, 4 doubles] since the last clearing read: episodes finished, sum of their returns, sum of their lengths, non-finite
+ * input elements left out of the statistics.  Synchronises. */
+int rex_norm_read_episodes(rex_t* h, double* out, int clear);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

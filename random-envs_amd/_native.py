@@ -17,6 +17,8 @@ SYMBOLS = [
     "rex_get_counters", "rex_enable_timing", "rex_read_timing", "rex_last_error", "rex_version",
     "rex_get_counters_state", "rex_set_counters_state", "rex_sample_task", "rex_set_info_buffer", "rex_export_lane", "rex_get_aux", "rex_set_aux", "rex_replay",
     "rex_get_launch_shape", "rex_set_launch_shape",
+    "rex_norm_enable", "rex_norm_set_training", "rex_norm_reset", "rex_norm_step", "rex_norm_get_stats", "rex_norm_set_stats",
+    "rex_norm_get_lane_state", "rex_norm_set_lane_state", "rex_norm_read_episodes",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -28,6 +30,12 @@ class RexDims(ctypes.Structure):
                 ("task_dim", ctypes.c_int), ("frame_skip", ctypes.c_int), ("max_episode_steps", ctypes.c_int),
                 ("discrete_action", ctypes.c_int), ("dt", ctypes.c_float), ("act_low", ctypes.c_float),
                 ("act_high", ctypes.c_float), ("n_info", ctypes.c_int), ("n_aux", ctypes.c_int)]
+
+
+class RexNormConfig(ctypes.Structure):
+    _fields_ = [("gamma", ctypes.c_double), ("epsilon", ctypes.c_double), ("clip_obs", ctypes.c_double),
+                ("clip_reward", ctypes.c_double), ("norm_obs", ctypes.c_int), ("norm_reward", ctypes.c_int),
+                ("training", ctypes.c_int)]
 
 
 class RexError(RuntimeError):
@@ -81,6 +89,16 @@ def lib():
     L.rex_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_get_aux.argtypes = [vp, vp, vp]
     L.rex_set_aux.argtypes = [vp, vp, vp]
+    dp = ctypes.POINTER(ctypes.c_double)
+    L.rex_norm_enable.argtypes = [vp, ctypes.POINTER(RexNormConfig)]
+    L.rex_norm_set_training.argtypes = [vp, i32]
+    L.rex_norm_reset.argtypes = [vp, vp, vp, vp, vp]
+    L.rex_norm_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_norm_get_stats.argtypes = [vp, dp]
+    L.rex_norm_set_stats.argtypes = [vp, dp]
+    L.rex_norm_get_lane_state.argtypes = [vp, vp, vp, vp, vp]
+    L.rex_norm_set_lane_state.argtypes = [vp, vp, vp, vp, vp]
+    L.rex_norm_read_episodes.argtypes = [vp, dp, i32]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

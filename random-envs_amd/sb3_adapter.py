@@ -45,6 +45,10 @@ class _AdapterBody:
             term = info["terminal_observation"].cpu().numpy()
             for i in np.nonzero(d)[0]:
                 infos[i] = {"terminal_observation": term[i], "TimeLimit.truncated": bool(trunc[i])}
+            if "episode_return" in info:   # over a NormalizedVecRandomEnv: the VecMonitor convention (vec_monitor.py: {"r": return, "l": length})
+                er, el = info["episode_return"].cpu().numpy(), info["episode_length"].cpu().numpy()
+                for i in np.nonzero(d)[0]:
+                    infos[i]["episode"] = {"r": float(er[i]), "l": int(el[i])}
         return obs.cpu().numpy(), rew.cpu().numpy(), d, infos
 
     def step(self, actions):
