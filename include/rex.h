@@ -257,6 +257,62 @@ int rex_norm_set_lane_state(rex_t* h, const double* ret, const double* ep_return
  * input elements left out of the statistics.  Synchronises. */
 int rex_norm_read_episodes(rex_t* h, double* out, int clear);
 
+/* ---- on-policy rollout buffer: fused store of a step, GAE(lambda), advantage statistics, minibatch gather ----------------------
+ * The layer above step() (and above rex_norm_step, when used) in every on-policy loop: stable-baselines3's RolloutBuffer
+ * (common/buffers.py: add, compute_returns_and_advantage, get) and the time-limit bootstrap of collect_rollouts
+ * (common/on_policy_algorithm.py).  No reference counterpart of its own.  rex_step and rex_norm_* are untouched.
+ *
+ * Storage belongs to the caller and uses the SoA layout of this interface, T = steps per rollout, B = the handle's batch:
+ *   obs [T][obs_dim][B] f32, action [T][act_dim][B] 4-byte words (copied bit for bit: float, or the cart-pole's int32),
+ *   reward / value / log_prob / advantage / returns [T][B] f32, done [T][B] uint8.
+ * The handle contributes the device, the dims and B, and holds no rollout state: slot indices are arguments, so a rollout captured
+ * into a graph replays correctly.  rex_rollout_enable makes the only allocation (a fixed-size scratch for the reduction partials,
+ * independent of T, plus the result and counter words; it synchronises); every other rex_rollout_* call before it returns
+ * REX_ERR_STATE.  The launching calls neither allocate nor synchronise. */
+typedef struct rex_rollout_buffers {
+  float* obs;
+  void* action;
+  float* reward;
+  float* value;
+  float* log_prob;
+  float* advantage;
+  float* returns;
+  uint8_t* done;
+  int64_t T;
+} rex_rollout_buffers;
+int rex_rollout_enable(rex_t* h);
+/* RolloutBuffer.add: ONE launch copies obs (the observation the action was computed from), action, reward, done, value, log_prob
+ * [dev, one step each, SoA] into slot t.  truncated [dev, uint8 batch] and terminal_value [dev, float batch] are optional and go
+ * together: on lanes with truncated != 0 the stored reward is (float)((double)reward + gamma * (double)terminal_value) -- a product
+ * and a sum in fp64, not fused, rounded once.  t outside [0, T): REX_ERR_ARG. */
+int rex_rollout_add(rex_t* h, const rex_rollout_buffers* buf, int64_t t, const float* obs, const void* action, const float* reward,
+                    const uint8_t* done, const float* value, const float* log_prob, const uint8_t* truncated, const float* terminal_value,
+                    double gamma, void* stream);
+/* RolloutBuffer.compute_returns_and_advantage in ONE launch (one thread per env, serial in t); done[t] is the flag step t returned,
+ * last_value [dev, float batch] the value of the observation after the last step.  For t = T-1 .. 0 per lane, every operand widened
+ * to fp64 and every operation a separate IEEE fp64 operation in the order written (A = 0 before t = T-1):
+ *   nnt = done[t] ? 0 : 1;  nv = (t == T-1) ? last_value : value[t+1];
+ *   delta = (reward[t] + (gamma * nv) * nnt) - value[t];  A = delta + ((gamma * lambda) * nnt) * A;
+ *   advantage[t] = (float)A;  returns[t] = (float)(A + value[t]).
+ * The result does not depend on the launch shape and equals a numpy fp64 restatement bit for bit. */
+int rex_rollout_gae(rex_t* h, const rex_rollout_buffers* buf, const float* last_value, double gamma, double lambda, void* stream);
+/* (n, mean, M2) of the whole advantage buffer in fp64, TWO launches: one partial per block (the count is a function of T * B only),
+ * merged in a fixed order -- runs of 4 partials in index order, then the runs pairwise over neighbours, a tree whose shape depends on the
+ * partial count only -- so two runs agree bit for bit.
+ * Non-finite elements are left out and counted.  normalise != 0: the second launch also rewrites advantage in place as
+ * (float)((A - mean) / (sqrt(M2 / (n - 1)) + 1e-8)) (the unbiased deviation, as torch.std gives it to SB3's PPO; NaN for n <= 1). */
+int rex_rollout_adv_stats(rex_t* h, const rex_rollout_buffers* buf, int normalise, void* stream);
+/* out [host, 4 doubles] of the last rex_rollout_adv_stats: n, mean, M2, non-finite elements left out.  Synchronises. */
+int rex_rollout_get_adv_stats(rex_t* h, double* out);
+/* RolloutBuffer.get for one minibatch, ONE launch: index [dev, int64 n] holds flat sample ids s = t * B + b; the outputs use the
+ * learner's layout and are each optional (NULL skips): obs_out [n][obs_dim] and action_out [n][act_dim] ROW-MAJOR, advantage_out /
+ * returns_out / value_out / log_prob_out [n].  A pure copy.  An id outside [0, T * B) is never dereferenced: that sample's outputs
+ * are zeros and a device counter is incremented (rex_rollout_read_bad_indices). */
+int rex_rollout_gather(rex_t* h, const rex_rollout_buffers* buf, const int64_t* index, int64_t n, float* obs_out, void* action_out,
+                       float* advantage_out, float* returns_out, float* value_out, float* log_prob_out, void* stream);
+/* out [host, 1 int64]: out-of-range sample ids rex_rollout_gather met since the last clearing read.  Synchronises. */
+int rex_rollout_read_bad_indices(rex_t* h, int64_t* out, int clear);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

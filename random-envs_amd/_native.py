@@ -19,6 +19,8 @@ SYMBOLS = [
     "rex_get_launch_shape", "rex_set_launch_shape",
     "rex_norm_enable", "rex_norm_set_training", "rex_norm_reset", "rex_norm_step", "rex_norm_get_stats", "rex_norm_set_stats",
     "rex_norm_get_lane_state", "rex_norm_set_lane_state", "rex_norm_read_episodes",
+    "rex_rollout_enable", "rex_rollout_add", "rex_rollout_gae", "rex_rollout_adv_stats", "rex_rollout_get_adv_stats", "rex_rollout_gather",
+    "rex_rollout_read_bad_indices",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -36,6 +38,10 @@ class RexNormConfig(ctypes.Structure):
     _fields_ = [("gamma", ctypes.c_double), ("epsilon", ctypes.c_double), ("clip_obs", ctypes.c_double),
                 ("clip_reward", ctypes.c_double), ("norm_obs", ctypes.c_int), ("norm_reward", ctypes.c_int),
                 ("training", ctypes.c_int)]
+
+
+class RexRolloutBuffers(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "action", "reward", "value", "log_prob", "advantage", "returns", "done")] + [("T", ctypes.c_int64)]
 
 
 class RexError(RuntimeError):
@@ -99,6 +105,14 @@ def lib():
     L.rex_norm_get_lane_state.argtypes = [vp, vp, vp, vp, vp]
     L.rex_norm_set_lane_state.argtypes = [vp, vp, vp, vp, vp]
     L.rex_norm_read_episodes.argtypes = [vp, dp, i32]
+    bp, f64 = ctypes.POINTER(RexRolloutBuffers), ctypes.c_double
+    L.rex_rollout_enable.argtypes = [vp]
+    L.rex_rollout_add.argtypes = [vp, bp, i64, vp, vp, vp, vp, vp, vp, vp, vp, f64, vp]
+    L.rex_rollout_gae.argtypes = [vp, bp, vp, f64, f64, vp]
+    L.rex_rollout_adv_stats.argtypes = [vp, bp, i32, vp]
+    L.rex_rollout_get_adv_stats.argtypes = [vp, dp]
+    L.rex_rollout_gather.argtypes = [vp, bp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rollout_read_bad_indices.argtypes = [vp, ctypes.POINTER(i64), i32]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L
