@@ -13,20 +13,7 @@
 #include <type_traits>
 
 #include "planar_spec.hpp"   // REX_HD
-
-// Diagnostic build (-DREX_KTIME): s_memtime deltas summed in per-lane registers (Kin::tacc) and flushed once per kernel by
-// the caller (wave maximum per slot), so the probes do not perturb what they measure.
-#if defined(REX_KTIME) && defined(__HIP_DEVICE_COMPILE__)
-#define REX_HSTAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define REX_HACC(K, slot, t0, t1) ((K).tacc[slot] += (t1) - (t0))
-#define REX_HCNT(K, slot, v) ((K).tacc[slot] += (unsigned long long)(v))
-#else
-#define REX_HSTAMP(var) ((void)0)
-#define REX_HACC(K, slot, t0, t1) ((void)0)
-#define REX_HCNT(K, slot, v) ((void)0)
-#endif
-enum { HT_SMOOTH = 0, HT_LIMITS, HT_BROAD, HT_NARROW_LOOP, HT_PAIR, HT_ROWS, HT_FACTOR, HT_BUILD_A, HT_SWEEPS, HT_QACC, HT_FORWARD,
-       HC_EVALS, HC_PAIR_CALLS, HC_ROW_CALLS, HC_SWEEPS, HC_NEFC, HT_SLOTS };
+#include "probes.hpp"        // REX_HSTAMP / REX_HACC / REX_HCNT, the HT_* / HC_* slots: empty in the product build
 
 namespace rex {
 namespace hum {
@@ -148,15 +135,7 @@ template <> REX_HD float fast_sqrt<float>(float a) { return __builtin_amdgcn_sqr
 template <class T> REX_HD T habs(T a) { return a < T(0) ? -a : a; }
 template <class T> REX_HD T hmax(T a, T b) { return a > b ? a : b; }
 template <class T> REX_HD T hmin(T a, T b) { return a < b ? a : b; }
-REX_HD void hsincos(float a, float& s, float& c) {
-#if defined(REX_LIBM_SINCOS) && defined(__HIP_DEVICE_COMPILE__)
-  sincosf(a, &s, &c);
-#elif defined(REX_LIBM_SINCOS)
-  s = sinf(a); c = cosf(a);
-#else
-  sincos_poly(a, s, c);
-#endif
-}
+REX_HD void hsincos(float a, float& s, float& c) { sincos_poly(a, s, c); }
 REX_HD void hsincos(double a, double& s, double& c) { s = sin(a); c = cos(a); }
 
 template <class T> REX_HD T dot3(const T* a, const T* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -229,9 +208,7 @@ template <class T>
 struct Kin {
   T qfrc_smooth[NV], qacc_smooth[NV];
   int ncon, nefc, overflow;       // contacts / constraint rows of this evaluation; overflow: some were dropped (MAXCON / MAXEFC)
-#if defined(REX_KTIME)
-  unsigned long long tacc[HT_SLOTS];
-#endif
+  REX_HTACC_MEMBER                // (probe builds: the lane's cycle / count accumulators, probes.hpp)
 };
 
 // host stand-in for the lane's LDS column (empty for the fp32 device lanes)

@@ -24,9 +24,6 @@
 #pragma once
 #include "humanoid_engine.hpp"
 
-#if defined(REX_KTIME) && defined(__HIP_DEVICE_COMPILE__)
-namespace rex { extern __device__ unsigned long long g_ktime[24 + 72]; }   // [24 + lvl]: wave-evaluations per sweep level, [40 + lvl]: their sweep cycles
-#endif
 namespace rex {
 namespace hum {
 namespace pr {
@@ -103,9 +100,7 @@ template <class T>
 struct PKin {
   T qfrc_smooth[LD], qacc_smooth[LD];
   int ncon, nefc, overflow;
-#if defined(REX_KTIME)
-  unsigned long long tacc[HT_SLOTS];
-#endif
+  REX_HTACC_MEMBER                // (probe builds: the lane's cycle / count accumulators, probes.hpp)
 };
 
 // observation inputs of the LAST evaluation (random_humanoid.py:193-204), local view
@@ -872,11 +867,7 @@ REX_HD int solve_pgs_dual(const P& p, const Model<T>& m, const PFactor<T>& F, PK
     default: it = pgs_sweeps_seg<DUAL_NMAX>(p, m, col, f); break;
   }
   REX_HSTAMP(p2); REX_HACC(K, HT_SWEEPS, p1, p2); REX_HCNT(K, HC_SWEEPS, it);
-#if defined(REX_KTIME) && defined(__HIP_DEVICE_COMPILE__)
-  { int nm = n; for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(nm, off); nm = o > nm ? o : nm; }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&g_ktime[24 + lvl], 1ull); atomicAdd(&g_ktime[40 + lvl], p2 - p1); atomicAdd(&g_ktime[56 + lvl], p1 - p0);
-                                   atomicAdd(&g_ktime[72 + (nm < 23 ? nm : 23)], 1ull); } }   // [72 + n]: wave-evaluations by their largest row count
-#endif
+  REX_HSWEEP_LEVEL(lvl, n, p0, p1, p2);
   T x[LD];
   for (int k = 0; k < LD; k++) x[k] = 0;
   static_for<0, DUAL_NMAX / 3>([&](auto CC) {

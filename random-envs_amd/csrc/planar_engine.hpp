@@ -18,20 +18,11 @@
 #include <stdio.h>
 
 #include "planar_spec.hpp"
+#include "probes.hpp"   // REX_MARK / REX_PSTAMP / REX_COUNT / REX_STAMP ...: empty in the product build
 
 namespace rex {
 
-REX_HD void sincos_t(float a, float& s, float& c) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(REX_FAST_SINCOS)
-  s = __sinf(a); c = __cosf(a);
-#elif defined(REX_LIBM_SINCOS) && defined(__HIP_DEVICE_COMPILE__)
-  sincosf(a, &s, &c);
-#elif defined(REX_LIBM_SINCOS)
-  s = sinf(a); c = cosf(a);
-#else
-  sincos_poly(a, s, c);
-#endif
-}
+REX_HD void sincos_t(float a, float& s, float& c) { sincos_poly(a, s, c); }
 REX_HD void sincos_t(double a, double& s, double& c) { s = sin(a); c = cos(a); }
 REX_HD float sqrt_t(float a) { return sqrtf(a); }
 REX_HD double sqrt_t(double a) { return sqrt(a); }
@@ -572,42 +563,7 @@ REX_HD void make_self_rows(const T (&v)[S::NV], const PlanarGeom<T, S>& G, const
   R.mask = mask;
 }
 
-// -DREX_MARKS: comment markers in the ISA (profiles/isa_regions.py counts the instructions between them)
-#if defined(REX_MARKS) && defined(__HIP_DEVICE_COMPILE__)
-#define REX_MARK(name) asm volatile("; REXMARK " name)
-#else
-#define REX_MARK(name) ((void)0)
-#endif
-
-#if (defined(REX_WAVETIME) || defined(REX_PHASES)) && !defined(REX_NOPHASES) && defined(__HIP_DEVICE_COMPILE__)
-// diagnostic build only: cycles per phase of forward(), summed per wave (lane 0) with fire-and-forget atomics.  The stamp
-// takes a value the phase produced as an input, so that value is complete before the clock is read.
-extern __device__ unsigned long long g_evalphase[8192][16];
-#define REX_PSTAMP(var, dep) unsigned long long var; { float dep_ = (float)(dep); asm volatile("s_nop 0\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) : "v"(dep_) : "memory"); }
-#define REX_PACC(slot, t0, t1) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_evalphase[blockIdx.x & 8191][slot], (t1) - (t0)); } while (0)
-#else
-#define REX_PSTAMP(var, dep) ((void)0)
-#define REX_PACC(slot, t0, t1) ((void)0)
-#endif
-
 struct SolveStats { int iters; bool capped; int mode; };   // mode: solver instantiation forward() entered (0 none, 1 general, 2 general + self rows, 3 feet-only straight-line)
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-struct GlobalStats { long solves, iters, pass1, pass2, ls_evals, nocon, slots_active; long toggles[4][4]; int trace[64], ntrace; };   // trace: mode * 100 + Newton iterations of the last solves
-inline GlobalStats& gstats() { static GlobalStats g{}; return g; }
-#define REX_COUNT(field, n) (gstats().field += (n))
-#elif defined(REX_KSTATS) && defined(__HIP_DEVICE_COMPILE__)
-// diagnostic build only: wave-level event counts (lane 0 of each wave adds)
-extern __device__ unsigned long long g_kstats[8];
-enum { KS_solves = 0, KS_iters = 1, KS_pass1 = 2, KS_pass2 = 3, KS_ls_evals = 4, KS_nocon = 5, KS_slots_active = 6 };
-#define REX_COUNT(field, n) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_kstats[KS_##field], (unsigned long long)(n)); } while (0)
-#elif defined(REX_WAVETIME) && defined(__HIP_DEVICE_COMPILE__)
-// diagnostic build only: the same counts per WAVE (slot = workgroup index), next to the wave's cycle count
-extern __device__ unsigned long long g_waveinfo[8192][8];
-enum { KS_solves = 0, KS_iters = 1, KS_pass1 = 2, KS_pass2 = 3, KS_ls_evals = 4, KS_nocon = 5, KS_slots_active = 6, KS_selfpath = 7 };
-#define REX_COUNT(field, n) do { if ((threadIdx.x & 63) == 0) g_waveinfo[blockIdx.x & 8191][KS_##field] += (unsigned long long)(n); } while (0)
-#else
-#define REX_COUNT(field, n) ((void)0)
-#endif
 
 // ---- Woodbury correction after a full Newton step: shared pieces ---------------------------------------------------------------------------
 // x1 = x + sr minimises the quadratic model of the set A its Hessian H was built for.  If the set at x1 differs from A in a few GROUPS of rows
@@ -767,11 +723,7 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
   T Ma[S::NV];   // M qacc: formed once, then carried along the accepted steps (Ma += alpha * M sr)
   sym_matvec<T, S>(M, qacc, Ma);
   bool ma_dirty = false;   // wave-uniform: a single-row correction moved qacc without updating Ma
-#if defined(REX_DIAG_MAXIT)   // timing diagnostics only (wrong results): cap the Newton iterations of every solve
-  const int maxit = REX_DIAG_MAXIT;
-#else
   constexpr int maxit = MAXIT;
-#endif
   for (int it = 0; it < maxit; ++it) {
     if (!REX_WAVE_ANY(!lane_done)) break;
     T cpx[NC], cpz[NC];   // per-iteration opaque copies of the contact points (see opaque())
@@ -836,9 +788,6 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     }
     T gn = T(0);
     static_for<0, S::NV>([&](auto II) { gn += g[II] * g[II]; });
-#if defined(REX_DEBUG_SOLVER) && !defined(__HIP_DEVICE_COMPILE__)
-    if (it >= 12) printf("  it %d gn/fref %.3e con_mask %x e1 %x e2 %x e3 %x lim %x\n", it, double(gn / fref), C.con_mask, e1, e2, e3, lim_on);
-#endif
     const bool same_set = lim_on == p_lim && e1 == p_e1 && e2 == p_e2 && e3 == p_e3 && self_on == p_self;
     p_lim = lim_on; p_e1 = e1; p_e2 = e2; p_e3 = e3; p_self = self_on;
     lane_done = lane_done || same_set || !(gn > tol2 * fref);   // NaN counts as done
@@ -989,9 +938,6 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     a = lane_done ? T(0) : a;
     T amax = T(0), smax = T(0);
     static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; Ma[II] += a * Ms[II]; amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
-#if defined(REX_DEBUG_SOLVER) && !defined(__HIP_DEVICE_COMPILE__)
-    if (it >= 12) printf("     alpha %.6g smax %.3e amax %.3e d1 %.3e d0 %.3e\n", double(a), double(smax), double(amax), double(d1), double(d0));
-#endif
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);   // stagnation at rounding level
     REX_PSTAMP(s_u, qacc[0] + amax + smax);
     REX_PACC(10, s_d, s_u);
@@ -1007,10 +953,7 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     // set at x2 equals the set at x1 (then it is that set's exact minimiser); otherwise the regular iterations go on from x2.
     // PAIR: the lane that owns the toggled slot computes the step, the other one contributes zero; limits: the even lane.
     if constexpr (!BR && !SELF) {
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-      { const int nl = __builtin_popcount(lim_on ^ m_lim), ns = __builtin_popcount((e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3));
-        if (!lane_done && a == T(1)) gstats().toggles[nl < 3 ? nl : 3][ns < 3 ? ns : 3]++; }
-#endif
+      REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
       // groups are dealt to the two lanes of a pair; host builds deal them to two virtual lanes of the one lane (same arithmetic, so the CPU
       // tests cover it); the one-lane device kernels keep the single-group form (a second group there is two more solves and their registers)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1068,14 +1011,8 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
           if (act && x0 < T(0)) v1 |= 1u << (k + par); if (act && x1 < T(0)) v2 |= 1u << (k + par); if (act && x2 < T(0)) v3 |= 1u << (k + par);
         });
         if constexpr (PAIR) { v1 |= pair_xchg(v1); v2 |= pair_xchg(v2); v3 |= pair_xchg(v3); }
-#if defined(REX_DIAG_CORR) && REX_DIAG_CORR >= 1
-        const bool ok2 = true;
-#else
         const bool ok2 = v_lim == m_lim && v1 == m_e1 && v2 == m_e2 && v3 == m_e3;
-#endif
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-        if (can) { gstats().toggles[3][3]++; if (ok2) gstats().toggles[3][2]++; }   // corrections tried / accepted
-#endif
+        REX_STAT_CORRECTION(can, ok2);
         lane_done = lane_done || (can && ok2);
         // x2 was computed for the set at x1: that is what the next gradient pass compares with
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3;
@@ -1610,10 +1547,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);
     // ---- one-group correction (see solve_newton): one joint limit or the edges of ONE unit toggled along a full step ----------------------
     {
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-      { const int nl = __builtin_popcount(lim_on ^ m_lim), ns = __builtin_popcount((e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3));
-        if (!lane_done && a == T(1)) gstats().toggles[nl < 3 ? nl : 3][ns < 3 ? ns : 3]++; }
-#endif
+      REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
 #if defined(__HIP_DEVICE_COMPILE__)
       constexpr int CMODE = PAIR ? 1 : 0;
 #else
@@ -1688,9 +1622,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
             ok2 = ok2 && ((((R.mask >> r) & 1u) && jar < T(0)) == (((m_self >> r) & 1u) != 0u));
           }
         }
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-        if (can) { gstats().toggles[3][3]++; if (ok2) gstats().toggles[3][2]++; }   // corrections tried / accepted
-#endif
+        REX_STAT_CORRECTION(can, ok2);
         lane_done = lane_done || (can && ok2);
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3; p_self = can ? m_self : p_self;
         ma_dirty = true;
@@ -1702,16 +1634,6 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
   }
   return st;
 }
-
-#if defined(REX_KTIME) && defined(__HIP_DEVICE_COMPILE__)
-// diagnostic build only: per-phase cycle stamps (s_memtime), summed per wave into g_ktime[]
-extern __device__ unsigned long long g_ktime[24 + 72];
-#define REX_STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define REX_TACC(slot, t0, t1) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_ktime[slot], (t1) - (t0)); } while (0)
-#else
-#define REX_STAMP(var) ((void)0)
-#define REX_TACC(slot, t0, t1) ((void)0)
-#endif
 
 // one forward-dynamics evaluation: qacc(q, v, ctrl)  ([3P] mj_forward)
 // GEN: which code the general solver modes (1, 2) run -- 0 the unrolled per-slot instantiations, 1 the rolled ROW-list solver (the hopper's
@@ -1748,12 +1670,7 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
   REX_PSTAMP(p_3, C.dist[2 * S::NG - 1] + C.lD[S::NB - 1] + T(C.self_possible));
   REX_STAMP(t_4);
   SolveStats st{0, false, 0};
-#if defined(REX_KSTATS) && defined(__HIP_DEVICE_COMPILE__)
-  { unsigned um = 0; for (int k = 0; k < 2 * S::NG; k++) if (REX_WAVE_ANY((C.con_mask >> k) & 1u)) um |= 1u << k;
-    REX_COUNT(solves, 1); if (!REX_WAVE_ANY(C.any)) REX_COUNT(nocon, 1); REX_COUNT(slots_active, __popc(um)); }
-#else
-  REX_COUNT(solves, 1); if (!C.any) REX_COUNT(nocon, 1); REX_COUNT(slots_active, __builtin_popcount(C.con_mask));
-#endif
+  REX_COUNT_SOLVE(C, 2 * S::NG);
   // Capsule-capsule self contacts (hopper): the bounding-circle cull is loose -- a sharply folded leg passes it for hundreds of
   // steps without touching -- and the kernel time at B = 32 768 is the SLOWEST wave's, so the dearer solver instantiation is
   // entered only when the narrow phase has actually produced a row somewhere in the wave.
@@ -1761,9 +1678,7 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
   bool self_rows = false;
   if constexpr (S::NSELF > 0) {
     if (REX_WAVE_ANY(C.self_possible != 0u)) {
-#if defined(REX_WAVETIME) && defined(__HIP_DEVICE_COMPILE__)
-      REX_COUNT(selfpath, 1);
-#endif
+      REX_WCOUNT(selfpath, 1);
       make_self_rows<T, S>(v, G, sp, K, C.self_possible, R);
       self_rows = REX_WAVE_ANY(R.mask != 0u);
     }
@@ -1804,9 +1719,6 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
       st = solve_newton<T, S, false, FAST, false>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     }
   }
-#if defined(REX_DIAG_NOGENERAL)   // timing diagnostics only (WRONG results for waves that leave the feet-only path): what the general instantiations cost the kernel by being in it
-  else if (mode == 1 || mode == 2) static_for<0, S::NV>([&](auto II) { qacc[II] = a0[II]; });
-#else
   else if (GEN == 2 && (mode == 1 || mode == 2)) {   // the LIST solver: one instantiation for both modes (a lane without self rows has R.mask == 0)
     if constexpr (GEN == 2) {
       constexpr unsigned UNITS = PAIR ? (ALL & 0x55555555u) : ALL;   // PAIR: the even slot 2 g holds the lane's own end (detect_constraints<PAIR>)
@@ -1839,26 +1751,17 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
       st = solve_newton<T, S, false, ALL, true>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     }
   }
-#endif
   else static_for<0, S::NV>([&](auto II) { qacc[II] = a0[II]; });
-#if defined(REX_KSTATS) && defined(__HIP_DEVICE_COMPILE__)
-  if (mode == 3 && (threadIdx.x & 63) == 0) atomicAdd(&g_kstats[7], 1ull);   // wave-solves on the fast path
-#endif
-#if defined(REX_WAVETIME) && defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (S::NSELF == 0) { if (mode == 1) REX_COUNT(selfpath, 1); }   // (slot "selfpath" of a chain without self pairs: general-path solves)
-#endif
+  if (mode == 3) REX_KCOUNT(fastpath, 1);   // wave-solves on the fast path
+  if constexpr (S::NSELF == 0) { if (mode == 1) REX_WCOUNT(selfpath, 1); }   // (slot "selfpath" of a chain without self pairs: general-path solves)
   REX_MARK("forward_end");
-#if defined(REX_STATS) && !defined(__HIP_DEVICE_COMPILE__)
-  gstats().trace[gstats().ntrace++ & 63] = st.iters + 100 * mode;
-#endif
+  REX_STAT_TRACE(st.iters + 100 * mode);
   REX_PSTAMP(p_5, qacc[0] + qacc[S::NV - 1]);
   REX_PACC(0, p_0, p_1); REX_PACC(1, p_1, p_2); REX_PACC(2, p_2, p_3); REX_PACC(3, p_3, p_4); REX_PACC(4, p_4, p_5);
   st.mode = mode;
   REX_STAMP(t_5);
   REX_TACC(0, t_0, t_1); REX_TACC(1, t_1, t_2); REX_TACC(2, t_2, t_3); REX_TACC(3, t_3, t_4); REX_TACC(4, t_4, t_5);
-#if defined(REX_KTIME) && defined(__HIP_DEVICE_COMPILE__)
-  if ((threadIdx.x & 63) == 0) atomicAdd(&g_ktime[7], 1ull);
-#endif
+  REX_TCNT(7, 1);   // evaluations
   return st;
 }
 

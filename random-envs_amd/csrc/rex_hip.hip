@@ -1,17 +1,20 @@
-// rex_hip.hip -- HIP kernels (gfx950 / MI355X) + the C-ABI of include/rex.h.
+// rex_hip.hip -- the library's one HIP translation unit (gfx950 / MI355X): the host handle and the C-ABI of include/rex.h.
 //
-// Execution model: ONE ENVIRONMENT PER LANE, 64-lane workgroups (one wavefront each) so a batch
-// of B envs is B/64 independent waves spread over the 256 CUs.  State is SoA in HBM
-// (qpos[nq][B], qvel[nv][B], xi[dim][B], ...): lane i touches element i of every row, so every
-// global access of a wave is one contiguous 256-byte segment.  The whole per-env solve
-// (composite-inertia M, L^T D L, pyramidal contact rows, Newton) lives in VGPRs
-// (planar_engine.hpp); hopper / half-cheetah model constants arrive as kernel arguments
-// (scalar registers), walker2d's per-env geometry as SoA rows.  No LDS, no MFMA: these are
-// tiny per-instance solves, not dense contractions.
+// The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
+// humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
+// math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp, the post-passes vecnorm.hpp and rollout.hpp.  Profiling probes
+// live in probes.hpp and are empty in this build.
 //
-// reset()-time xi sampling and init-state noise use rocRAND's Philox4x32-10 device API with
-// subsequence = GLOBAL env index (handle env_offset + lane) and offset = f(episode, t): results
-// do not depend on how a batch is sharded over GPUs and no RNG state is stored.
+// Execution model: state is SoA in HBM (qpos[nq][B], qvel[nv][B], xi[dim][B], ...), a workgroup is ONE wavefront of up to 64 lanes, and
+// the launch shape follows the batch (rex_create; "Launch shape by batch" below).  While the GPU has a SIMD for every wave an environment
+// is split over TWO LANES (lanes 2 e and 2 e + 1 of a wave hold env e: planar chains up to 32 envs x SIMDs, the humanoid at every size);
+// past that the planar chains run one env per lane in full waves.  Either way lane accesses to a row are contiguous.  The planar per-env
+// solve (composite-inertia M, L^T D L, pyramidal contact rows, Newton) lives in VGPRs; hopper / half-cheetah model constants arrive as
+// kernel arguments (scalar registers), walker2d's per-env geometry as SoA rows.  LDS holds what must not occupy registers across the
+// solver: the planar step kernel parks t and episode there and its two-lanes-per-env shape runs the general (list) solver out of one LDS
+// column per lane; the humanoid keeps its dual PGS working set and the pair's hit queue in one column per env.  No MFMA: these are tiny
+// per-instance solves, not dense contractions.
+#define REX_PROBES_STORAGE 1   // this translation unit owns the probe storage and the rex_debug_* readers of probe builds (probes.hpp)
 #include <hip/hip_runtime.h>
 #include <rocrand/rocrand_kernel.h>
 
@@ -24,77 +27,15 @@
 #include <vector>
 
 #include "../../include/rex.h"
-#include "planar_model.hpp"
-#include "humanoid_model.hpp"
-#include "humanoid_pair.hpp"
 #include "vecnorm.hpp"
 #include "rollout.hpp"
+#include "dev_state.hpp"
+#include "device_rng.hpp"
+#include "cartpole_kernels.hpp"
+#include "planar_kernels.hpp"
+#include "humanoid_kernels.hpp"
 
 using namespace rex;
-
-// -DREX_ONLY_KIND=<rex_env_kind>: tuning builds that compile ONE chain's kernels (seconds instead of minutes);
-// the other kinds then fail in rex_create with REX_ERR_UNSUPPORTED.  The product build defines nothing.
-#ifdef REX_ONLY_KIND
-#define REX_EN_CARTPOLE (REX_ONLY_KIND == 0)
-#define REX_EN_HOPPER (REX_ONLY_KIND == 1)
-#define REX_EN_HALFCHEETAH (REX_ONLY_KIND == 2)
-#define REX_EN_WALKER2D (REX_ONLY_KIND == 3)
-#define REX_EN_HUMANOID (REX_ONLY_KIND == 4)
-#else
-#define REX_EN_CARTPOLE 1
-#define REX_EN_HOPPER 1
-#define REX_EN_HALFCHEETAH 1
-#define REX_EN_WALKER2D 1
-#define REX_EN_HUMANOID 1
-#endif
-
-#if defined(REX_KTIME)
-namespace rex { __device__ unsigned long long g_ktime[24 + 72]; }   // 0..7 planar phases, 8..23 humanoid phases, 24.. histogram of humanoid row counts
-extern "C" int rex_debug_ktime(unsigned long long* out) {   // diagnostic build only (not in rex.h)
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_ktime), sizeof(unsigned long long) * 96) != hipSuccess) return -1;
-  unsigned long long z[96] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rex::g_ktime), z, sizeof z); return 0; }
-#endif
-#if defined(REX_WAVETIME)
-// diagnostic build only: cycles every wave of the last planar / humanoid step launch spent in its substeps (the kernel time at
-// B = 32 768 is the SLOWEST wave's, not the average)
-namespace rex { __device__ unsigned long long g_wavetime[8192]; __device__ unsigned long long g_waveinfo[8192][8]; __device__ unsigned long long g_wavehum[1024][16];
-                __device__ unsigned long long g_wavephase[8192][4];
-                __device__ unsigned long long g_wavetail[8192][8];    // planar step kernel: what the tail of a wave (everything behind the substeps) spends where
-                __device__ unsigned long long g_waveplace[8192][4];   // 100 MHz clock at entry and exit, HW_ID, XCC_ID: where and when each wave ran
-                }
-#endif
-#if defined(REX_WAVETIME) || defined(REX_PHASES)
-namespace rex { __device__ unsigned long long g_evalphase[8192][16]; }   // forward(): kinematics, mass+bias, detect, dispatch+self, rows+solve, pass 1, pass 2, H, ldl+solve, phi', update, correction
-extern "C" int rex_debug_evalphase(unsigned long long* out, int n) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_evalphase), sizeof(unsigned long long) * 16 * (n < 8192 ? n : 8192)) != hipSuccess) return -1;
-  static unsigned long long z[8192][16]; return hipMemcpyToSymbol(HIP_SYMBOL(rex::g_evalphase), z, sizeof z) == hipSuccess ? 0 : -1; }
-#endif
-#if defined(REX_WAVETIME)
-// g_wavephase: planar step kernel, cycles entry -> state loaded -> substeps done -> outputs stored -> fused reset done
-extern "C" int rex_debug_wavephase(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavephase), sizeof(unsigned long long) * 4 * (n < 8192 ? n : 8192)) == hipSuccess ? 0 : -1; }
-// g_wavetail: cycles from the end of the substeps to [0] t and episode back from LDS, [1] reward / done / info stores issued; from there to [2] episode stored,
-// [3] reset state and observation drawn, [4] xi draws done and stored, [5] end of the reset path (walker2d: the re-derive); the one set of
-// state / obs stores follows.  [2..5] are maxima over the launches since the last read (zeroed here) and stay 0 for a wave that skipped the reset.
-extern "C" int rex_debug_wavetail(unsigned long long* out, int n) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavetail), sizeof(unsigned long long) * 8 * (n < 8192 ? n : 8192)) != hipSuccess) return -1;
-  static unsigned long long z[8192][8]; return hipMemcpyToSymbol(HIP_SYMBOL(rex::g_wavetail), z, sizeof z) == hipSuccess ? 0 : -1; }
-extern "C" int rex_debug_waveplace(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_waveplace), sizeof(unsigned long long) * 4 * (n < 8192 ? n : 8192)) == hipSuccess ? 0 : -1; }
-extern "C" int rex_debug_wavehum(unsigned long long* out) {   // humanoid: per-wave phase accumulators of the last launch (-DREX_KTIME -DREX_WAVETIME)
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavehum), sizeof(unsigned long long) * 1024 * 16) == hipSuccess ? 0 : -1; }
-extern "C" int rex_debug_waveinfo(unsigned long long* out, int n) {   // n waves x 8 counters, then zeroed
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_waveinfo), sizeof(unsigned long long) * 8 * (n < 8192 ? n : 8192)) != hipSuccess) return -1;
-  static unsigned long long z[8192][8]; return hipMemcpyToSymbol(HIP_SYMBOL(rex::g_waveinfo), z, sizeof z) == hipSuccess ? 0 : -1; }
-extern "C" int rex_debug_wavetime(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_wavetime), sizeof(unsigned long long) * (n < 8192 ? n : 8192)) == hipSuccess ? 0 : -1; }
-#endif
-#if defined(REX_KSTATS)
-namespace rex { __device__ unsigned long long g_kstats[8]; }
-extern "C" int rex_debug_kstats(unsigned long long* out) {   // diagnostic build only (not in rex.h)
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_kstats), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-  unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rex::g_kstats), z, sizeof z); return 0; }
-#endif
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -132,897 +73,11 @@ static const char* stray_knob() {   // a knob set without REX_ALLOW_TUNING=1, or
 }
 static const char* knob(const char* name) { return tuning_allowed() ? getenv(name) : nullptr; }
 
-// ------------------------------------------------------------------------------------------
-// DR distribution block (device-visible copy of RandomEnv's min/max/mean/stdev/cov state,
-// random_env.py:102-127)
-// ------------------------------------------------------------------------------------------
-constexpr int MAX_XI = 32;
-struct DRParams {
-  int type;                 // rex_dr_type
-  int dim;
-  float a[MAX_XI];          // uniform: lo   | truncnorm/gaussian: mean | fullgaussian: mean (normalised space)
-  float b[MAX_XI];          // uniform: hi   | truncnorm/gaussian: std
-  float lower[MAX_XI];      // get_task_lower_bound(i)
-  float lo[MAX_XI], hi[MAX_XI];   // fullgaussian: search bounds for denormalisation
-  int map[MAX_XI];          // task index -> row of the kernels' full xi block (identity for the regular ids;
-                            // the Unmodeled ids randomise a suffix only)
-  const float* chol;        // fullgaussian: lower Cholesky factor of cov, row-major [dim][MAX_XI], DEVICE memory
-};
-
-// Philox offsets per episode: [0, 256) init-state noise, [256, 512) xi draws, STEP_BASE + t * STEP_STRIDE the
-// observation noise of step t.  2^32 offsets per episode keep the step regions of consecutive episodes disjoint for
-// 2^26 steps (time_limit off / endless episodes run far past 500 steps); the Philox counter is 64-bit + 64-bit subsequence.
-constexpr unsigned long long EP_STRIDE = 1ull << 32;
-constexpr unsigned long long STEP_BASE = 512, STEP_STRIDE = 64;
-constexpr unsigned long long SAMPLE_SEED_SALT = 0x9E3779B97F4A7C15ull;   // rex_sample_task: a stream family of its own
-
-// truncated standard normal on [-2, 2] by inverse CDF (the method scipy.stats.truncnorm.rvs uses)
-__device__ __forceinline__ float truncnorm2(float u) {
-  const float Fa = 0.022750131948179195f, Fb = 0.9772498680518208f;   // Phi(-2), Phi(2)
-  float p = Fa + u * (Fb - Fa);
-  float x = normcdfinvf(p);
-  return fminf(fmaxf(x, -2.0f), 2.0f);
-}
-
-// RandomEnv.sample_task (random_env.py:148-203), one lane = one env.  Cold path (reset only): runtime dimension,
-// rolled loops, every draw stored straight to its xi row (no per-lane array => the kernel needs no scratch).
-// RNG: where the draws come from -- rocRAND's engine (EngineRng: the reset kernels, rex_sample_task) or the same word stream held in
-// registers (PhiloxWords, below: the planar step kernel's fused reset).
-struct EngineRng {
-  rocrand_state_philox4x32_10 st;
-  __device__ __forceinline__ EngineRng(unsigned long long seed, unsigned long long subseq, unsigned long long offset) { rocrand_init(seed, subseq, offset, &st); }
-  __device__ __forceinline__ float uniform() { return rocrand_uniform(&st); }
-  __device__ __forceinline__ float normal() { return rocrand_normal(&st); }
-};
-template <class RNG = EngineRng>
-__device__ void sample_task(const DRParams& dr, unsigned long long seed, unsigned long long subseq, unsigned long long offset,
-                            float* __restrict__ xi_rows, size_t B, unsigned i, unsigned long long* counters) {
-  const int d = dr.dim;
-  RNG st(seed, subseq, offset);
-  if (dr.type == REX_DR_UNIFORM) {           // :150-151  U(min, max) per dim
-    for (int k = 0; k < d; k++) { float u = st.uniform(); (xi_rows + (size_t)dr.map[k] * B)[i] = dr.a[k] + (dr.b[k] - dr.a[k]) * (1.0f - u); }
-  } else if (dr.type == REX_DR_TRUNCNORM) {  // :153-171 (intended semantics; the reference raises NameError)
-    for (int k = 0; k < d; k++) {
-      float lb = dr.lower[k];
-      float obs = dr.a[k] + dr.b[k] * truncnorm2(st.uniform());
-      // `attempts` 1,2 keep a redraw; the third redraw is overwritten by lower_bound (:162-167)
-      for (int att = 0; att < 2 && obs < lb; att++) obs = dr.a[k] + dr.b[k] * truncnorm2(st.uniform());
-      if (obs < lb) obs = lb;
-      (xi_rows + (size_t)dr.map[k] * B)[i] = obs;
-    }
-  } else if (dr.type == REX_DR_GAUSSIAN) {   // :173-190: redraw while < 0.1, raise after the 3rd failure
-    for (int k = 0; k < d; k++) {
-      float obs = dr.a[k] + dr.b[k] * st.normal();
-      for (int att = 0; att < 2 && obs < 0.1f; att++) obs = dr.a[k] + dr.b[k] * st.normal();
-      if (obs < 0.1f) { obs = 0.1f; atomicAdd(counters + 1, 1ull); }   // a device lane cannot raise: clamp + count
-      (xi_rows + (size_t)dr.map[k] * B)[i] = obs;
-    }
-  } else if (dr.type == REX_DR_FULLGAUSSIAN) {  // :192-198: MVN in normalised [0,4]^d, clip, denormalise (:205-220)
-    // x_k = mean_k + sum_{j<=k} L_kj z_j: the z stream is replayed from the counter for every k (no z[] array)
-    for (int k = 0; k < d; k++) {
-      RNG sz(seed, subseq, offset);
-      float acc = dr.a[k];
-      for (int j = 0; j <= k; j++) acc += dr.chol[k * MAX_XI + j] * sz.normal();
-      acc = fminf(fmaxf(acc, 0.0f), 4.0f);
-      (xi_rows + (size_t)dr.map[k] * B)[i] = acc * (dr.hi[k] - dr.lo[k]) * 0.25f + dr.lo[k];
-    }
-  }
-}
-
-// ---- counter-based Philox4x32-10 in registers (the planar step kernel's fused reset and observation noise) ----
-// The streams are stateless by design (subsequence = global env index, offset = f(episode, t), every region starts on a multiple of 4), so a
-// consumer that knows at compile time which words it needs has no use for the engine's state (four result words indexed by a runtime
-// `substate`, a look-ahead block on every 4th draw, a per-draw "block exhausted?" branch).  philox_block gives the four words the engine
-// returns for draws 4 b .. 4 b + 3 of rocrand_init(seed, subsequence, offset), `block` = offset / 4 + b: rocrand_philox4x32_10.h forms the
-// counter as (offset / 4 in .xy, subsequence in .zw) and the key from the seed (restart, discard_subsequence_impl, discard_impl), ten rounds.
-__device__ __forceinline__ void philox_block(unsigned long long seed, unsigned long long subseq, unsigned long long block, unsigned* __restrict__ w) {
-  unsigned c0 = (unsigned)block, c1 = (unsigned)(block >> 32), c2 = (unsigned)subseq, c3 = (unsigned)(subseq >> 32);
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-// NBLK consecutive blocks from `block0` into w[4 NBLK]; the blocks are independent, the compiler interleaves their rounds
-template <int NBLK>
-__device__ __forceinline__ void philox_blocks(unsigned long long seed, unsigned long long subseq, unsigned long long block0, unsigned (&w)[4 * NBLK]) {
-  static_for<0, NBLK>([&](auto BB) { constexpr int b = BB; philox_block(seed, subseq, block0 + (unsigned long long)b, w + 4 * b); });
-}
-// the conversions rocrand_uniform / rocrand_normal apply to the engine's words
-__device__ __forceinline__ float philox_uniform(unsigned w) { return rocrand_device::detail::uniform_distribution(w); }
-__device__ __forceinline__ float2 philox_normal2(unsigned w0, unsigned w1) { return rocrand_device::detail::normal_distribution2(w0, w1); }
-
-// The engine's draw sequence for consumers whose number of draws depends on the data (truncnorm / gaussian redraws): word j of the stream is
-// draw j, a block is evaluated when its first word is asked for (no look-ahead), the four words sit in registers and are picked by
-// selects, rocrand_normal's Box-Muller pairing (two words -> .x now, .y at the next call) is kept.  Offsets are multiples of 4.
-struct PhiloxWords {
-  unsigned long long seed, subseq, block; unsigned w[4]; int n; float saved; bool has;
-  __device__ __forceinline__ PhiloxWords(unsigned long long seed_, unsigned long long subseq_, unsigned long long offset)
-      : seed(seed_), subseq(subseq_), block(offset >> 2), n(4), saved(0.0f), has(false) {}
-  __device__ __forceinline__ unsigned next() {
-    if (n == 4) { philox_block(seed, subseq, block, w); block++; n = 0; }
-    const unsigned r = n == 0 ? w[0] : n == 1 ? w[1] : n == 2 ? w[2] : w[3];
-    n++;
-    return r;
-  }
-  __device__ __forceinline__ float uniform() { return philox_uniform(next()); }
-  __device__ __forceinline__ float normal() {
-    if (has) { has = false; return saved; }
-    const unsigned a = next(), b = next();
-    const float2 r = philox_normal2(a, b);
-    saved = r.y; has = true;
-    return r.x;
-  }
-};
-
-// sample_task's REX_DR_UNIFORM case for a compile-time bound on the dimension: draw k is word k of the stream, the parameters are fetched
-// in one batch before the draws and no store address waits on a scalar load of its own.  Same values, same stores.
-template <int NXI>
-__device__ __forceinline__ void sample_task_uniform(const DRParams& dr, unsigned long long seed, unsigned long long subseq, unsigned long long offset,
-                                                    float* __restrict__ xi_rows, size_t B, unsigned i) {
-  const int d = dr.dim;
-  float a[NXI], b[NXI]; int m[NXI];
-  static_for<0, NXI>([&](auto KK) { constexpr int k = KK; a[k] = dr.a[k]; b[k] = dr.b[k]; m[k] = dr.map[k]; });
-  constexpr int NBLK = (NXI + 3) / 4;
-  unsigned w[4 * NBLK];
-  static_for<0, NBLK>([&](auto BB) { constexpr int bb = BB; if (4 * bb < d) philox_block(seed, subseq, (offset >> 2) + (unsigned long long)bb, w + 4 * bb); });
-  static_for<0, NXI>([&](auto KK) { constexpr int k = KK;
-    if (k < d) { float u = philox_uniform(w[k]); (xi_rows + (size_t)m[k] * B)[i] = a[k] + (b[k] - a[k]) * (1.0f - u); } });
-}
-
-// ------------------------------------------------------------------------------------------
-// device-side state of one handle
-// ------------------------------------------------------------------------------------------
-struct DevState {
-  float* qpos; float* qvel; float* xi;     // SoA rows of length B
-  float* geom;                             // walker2d: per-env PlanarGeom rows [NGEOMF][B]; else null
-  float* aux;                              // humanoid: data.xipos[:,0] of the last forward, [14][B]; else null
-  int* t; unsigned* episode; unsigned char* done;
-  unsigned long long* counters;            // [4]
-  long long B, env_offset;
-  unsigned long long seed;
-};
-
-struct StepFlags {
-  int endless, noisy, time_limit, max_steps;
-  float noise_std;
-  float* info;   // optional per-term reward rows [n_info][B] (random_half_cheetah.py:110, random_humanoid.py:182-187); null = off
-  int readonly;  // rex_replay: state comes from the caller's buffers and nothing of the handle is written (no t / done / state stores, no reset)
-};
-
-// ------------------------------------------------------------------------------------------
-// CartPole (random_envs/random_cartpole.py:172-229).  qpos = (x, theta), qvel = (x_dot, theta_dot).
-// ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) cartpole_step_kernel(DevState s, StepFlags fl, const int* __restrict__ action,
-                                                           float* __restrict__ obs, float* __restrict__ reward,
-                                                           unsigned char* __restrict__ done_out, unsigned char* __restrict__ trunc_out,
-                                                           float* __restrict__ term_obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;
-  const long long B = s.B;
-  float x = s.qpos[i], th = s.qpos[B + i], xd = s.qvel[i], thd = s.qvel[B + i];
-  float g = s.xi[i], mc = s.xi[B + i], mp = s.xi[2 * B + i], l = s.xi[3 * B + i];
-  float total = mp + mc;                                  // set_task :166
-  const float pml = 0.1f * 0.5f;                          // :79, not refreshed by set_task
-  float force = action[i] == 1 ? 10.0f : -10.0f;          // :80,178
-  float st, ct; sincosf(th, &st, &ct);
-  float temp = (force + pml * thd * thd * st) / total;    // :184
-  float thacc = (g * st - ct * temp) / (l * (4.0f / 3.0f - mp * ct * ct / total));   // :185
-  float xacc = temp - pml * thacc * ct / total;           // :186
-  const float tau = 0.02f;
-  x = x + tau * xd; xd = xd + tau * xacc; th = th + tau * thd; thd = thd + tau * thacc;   // :188-192
-  s.qpos[i] = x; s.qpos[B + i] = th; s.qvel[i] = xd; s.qvel[B + i] = thd;
-  const float th_thr = 12.0f * 2.0f * 3.14159265358979323846f / 360.0f, x_thr = 2.4f;   // :84-85
-  bool was_done = s.done[i] != 0;                          // steps_beyond_done bookkeeping :208-222
-  bool dn = (x < -x_thr) || (x > x_thr) || (th < -th_thr) || (th > th_thr);
-  float r = (!dn) ? 1.0f : (was_done ? 0.0f : 1.0f);
-  int t = s.t[i] + 1; s.t[i] = t;
-  bool trunc = fl.time_limit && t >= fl.max_steps && !dn;
-  bool d = dn || trunc;
-  s.done[i] = (unsigned char)((dn || was_done) ? 1 : 0) | (unsigned char)(d ? 2 : 0);
-  obs[i] = x; obs[B + i] = xd; obs[2 * B + i] = th; obs[3 * B + i] = thd;   // np.array(self.state) :224
-  if (term_obs) { term_obs[i] = x; term_obs[B + i] = xd; term_obs[2 * B + i] = th; term_obs[3 * B + i] = thd; }
-  reward[i] = r; done_out[i] = d ? 1 : 0;
-  if (trunc_out) trunc_out[i] = trunc ? 1 : 0;
-}
-
-// reset(): state ~ U(-0.05, 0.05)^4 (random_cartpole.py:226-229). `resample` = set_random_task.
-__global__ void __launch_bounds__(64) cartpole_reset_kernel(DevState s, DRParams dr, int resample, int reset_state,
-                                                            const unsigned char* __restrict__ mask, int mask_bit,
-                                                            float* __restrict__ obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;
-  if (mask && !(mask[i] & mask_bit)) return;
-  const long long B = s.B;
-  unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
-  rocrand_state_philox4x32_10 st;
-  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
-  if (reset_state) {
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = -0.05f + 0.1f * (1.0f - rocrand_uniform(&st));
-    s.qpos[i] = v[0]; s.qvel[i] = v[1]; s.qpos[B + i] = v[2]; s.qvel[B + i] = v[3];
-    s.t[i] = 0; s.done[i] = 0;
-    if (obs) { obs[i] = v[0]; obs[B + i] = v[1]; obs[2 * B + i] = v[2]; obs[3 * B + i] = v[3]; }
-  }
-  if (resample && dr.type != REX_DR_NONE) {
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, i, s.counters);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// planar MuJoCo-style envs
-// ------------------------------------------------------------------------------------------
-template <class S> constexpr int geom_floats() { return sizeof(PlanarGeom<float, S>) / sizeof(float); }
-
-template <class S>
-__device__ __forceinline__ void load_geom(const DevState& s, unsigned i, const PlanarGeom<float, S>& uniform,
-                                          PlanarGeom<float, S>& G) {
-  if constexpr (S::KIND == 3) {   // walker2d: geometry is a function of the xi lengths (25 distinct values per env)
-    walker_expand(uniform, [&](int k) { return (s.geom + (size_t)k * s.B)[i]; }, G);
-  } else {
-    G = uniform;
-  }
-}
-
-// observation: concat(qpos[1:], qvel) (random_hopper.py:100-110, random_half_cheetah.py:112-121,
-// random_walker2d.py:133-142) + optional N(0, noise_var)
-template <class S>
-__device__ __forceinline__ void write_obs(const float (&q)[S::NV], const float (&v)[S::NV], float* __restrict__ obs,
-                                          long long B, unsigned i, bool noisy, float noise_std,
-                                          rocrand_state_philox4x32_10* st) {
-  static_for<0, S::NOBS>([&](auto KK) {
-    constexpr int k = KK;
-    float o = k < S::NV - 1 ? q[k + 1] : v[k - (S::NV - 1)];
-    if (noisy) o += noise_std * rocrand_normal(st);
-    (obs + (size_t)k * B)[i] = o;
-  });
-}
-
-// the same observation into registers; the noise of write_obs from the stream's blocks: rocrand_normal draws two words for observation 2 p
-// (Box-Muller .x) and hands the saved .y to observation 2 p + 1
-template <class S>
-__device__ __forceinline__ void obs_values(const float (&q)[S::NV], const float (&v)[S::NV], float (&ob)[S::NOBS], bool noisy, float noise_std,
-                                           unsigned long long seed, unsigned long long subseq, unsigned long long offset) {
-  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; ob[k] = k < S::NV - 1 ? q[k + 1] : v[k - (S::NV - 1)]; });
-  if (noisy) {
-    constexpr int NP = (S::NOBS + 1) / 2, NBLK = (2 * NP + 3) / 4;
-    unsigned w[4 * NBLK];
-    philox_blocks<NBLK>(seed, subseq, offset >> 2, w);
-    static_for<0, NP>([&](auto PP) { constexpr int p = PP;
-      const float2 n = philox_normal2(w[2 * p], w[2 * p + 1]);
-      ob[2 * p] += noise_std * n.x;
-      if constexpr (2 * p + 1 < S::NOBS) ob[2 * p + 1] += noise_std * n.y; });
-  }
-}
-// reset_model's state of episode `ep` (planar_reset_lane below draws the same words through the engine): word 2 k -> qpos[k], word 2 k + 1 ->
-// qvel[k]; half-cheetah: qvel is normal, a Box-Muller pair serves two velocities, so dofs 2 p and 2 p + 1 take words 4 p .. 4 p + 3 as
-// (qpos[2 p], pair, pair, qpos[2 p + 1])
-template <class S>
-__device__ __forceinline__ void reset_state_values(unsigned long long seed, unsigned long long subseq, unsigned ep, float (&q)[S::NV], float (&v)[S::NV]) {
-  constexpr int NV = S::NV;
-  constexpr int NW = S::KIND == 2 ? 4 * (NV / 2) + (NV % 2 ? 3 : 0) : 2 * NV, NBLK = (NW + 3) / 4;
-  unsigned w[4 * NBLK];
-  philox_blocks<NBLK>(seed, subseq, ((unsigned long long)ep * EP_STRIDE) >> 2, w);
-  const float c = S::INIT_NOISE;
-  if constexpr (S::KIND == 2) {
-    static_for<0, (NV + 1) / 2>([&](auto PP) { constexpr int p = PP;
-      const float2 n = philox_normal2(w[4 * p + 1], w[4 * p + 2]);                       // random_half_cheetah.py:125
-      q[2 * p] = c * (2.0f * (1.0f - philox_uniform(w[4 * p])) - 1.0f); v[2 * p] = 0.1f * n.x;
-      if constexpr (2 * p + 1 < NV) { q[2 * p + 1] = c * (2.0f * (1.0f - philox_uniform(w[4 * p + 3])) - 1.0f); v[2 * p + 1] = 0.1f * n.y; } });
-  } else {
-    static_for<0, NV>([&](auto KK) { constexpr int k = KK;
-      q[k] = c * (2.0f * (1.0f - philox_uniform(w[2 * k])) - 1.0f);                     // init_qpos + U(-c, c)
-      v[k] = c * (2.0f * (1.0f - philox_uniform(w[2 * k + 1])) - 1.0f); });
-    q[1] += 1.25f;                                                                      // init_qpos[1] = 1.25 (ref, hopper.xml:30)
-  }
-}
-
-template <class S>
-__device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepFlags& fl, const DRParams& dr, int resample,
-                                                  int reset_state, unsigned i, float* __restrict__ obs);
-// walker2d: the per-env model constants of lane i from its xi lengths (what build_model() does inside
-// RandomWalker2dEnv.set_task, random_walker2d.py:106-113)
-__device__ __forceinline__ void walker_derive_lane(const DevState& s, unsigned i, int refresh_frozen_masses);
-__device__ __attribute__((noinline)) void walker_derive_call(const DevState& s, unsigned i, int refresh_frozen_masses);
-// `resample` argument of the step kernel: bit 0 = set_random_task at reset, bit 1 = walker2d: re-derive the lane's geometry from its
-// new xi lengths right there (the auto-reset under DR used to cost a reset launch and a derive launch behind every step),
-// bit 2 = the Unmodeled id's frozen masses follow the new lengths
-constexpr int RS_RESAMPLE = 1, RS_DERIVE = 2, RS_REFRESH = 4;
-
-// Register budget of the planar step kernel: waves per SIMD the allocator must leave room for (512 registers per lane and
-// SIMD: 1 wave -> 512, 2 -> 256, 3 -> 168, 4 -> 128).  A lone wave issues one VALU instruction per 4 cycles, the SIMD one
-// per 2: the step kernel is VALU-issue bound (PMC: 1.0 quad-cycle per VALU instruction), so two narrower co-resident waves
-// beat one wide one as long as the live state fits.
-#ifndef REX_STEP_WAVES
-#define REX_STEP_WAVES 1
-#endif
-#define REX_STEP_OCC __attribute__((amdgpu_waves_per_eu(REX_STEP_WAVES, REX_STEP_WAVES)))
-
-// PAIR: two lanes per environment (lane 2i and 2i + 1 both hold env i; planar_spec.hpp "two lanes per environment"):
-// the launch has 2 B lanes in 64-lane blocks = 32 envs per wave, exactly the envs-per-wave of the 32-lane 1-lane-per-env
-// launch, but the wave is full and the per-slot work of the feet-only solver is split over the two lanes.
-// ROLLED: the general solver instantiation as runtime loops over a row list in scratch (planar_engine.hpp::solve_newton_rolled): the kernel
-// then fits 256 registers and is built for TWO waves per SIMD -- hopper handles with more full one-lane-per-env waves than the GPU has SIMDs (rex_create).
-template <class S, bool PAIR, bool ROLLED = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLLED ? 2 : REX_STEP_WAVES, ROLLED ? 2 : REX_STEP_WAVES)))
-planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
-                                                         SolParams<float> sp, const float* __restrict__ action,
-                                                         float* __restrict__ obs, float* __restrict__ reward,
-                                                         unsigned char* __restrict__ done_out,
-                                                         unsigned char* __restrict__ trunc_out, float* __restrict__ term_obs,
-                                                         DRParams dr, int fused_reset, int resample) {
-#if defined(REX_WAVETIME)
-  const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  // Narrow blocks (pair_lanes_for: 32 / 16 lanes) touch 64 / 32 bytes of every SoA row, so 2 / 4 neighbouring blocks share each 128-byte line.  Blocks are
-  // dealt round-robin over the 8 XCDs (b and b + 8 share one: MI355X_MICROARCH.md, workgroup dispatch), each with its own L2: in launch order
-  // the sharers sit on different XCDs and every line is fetched 2 / 4 times (C4: 4.4x the algorithmic bytes).  Transposed, block b works on the
-  // env group (b % 8) * (blocks / 8) + b / 8: neighbours in memory are neighbours on one XCD.  The groups themselves -- which envs share a wave --
-  // do not change, so neither does any result.
-  unsigned blk = blockIdx.x;
-  if constexpr (PAIR) { if (blockDim.x < 64u && (gridDim.x & 7u) == 0u) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3); }
-  const unsigned i = (blk * blockDim.x + threadIdx.x) >> (PAIR ? 1 : 0);   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;   // (both lanes of a pair leave together: i is the same)
-  const long long B = s.B;
-  // t and episode are wanted behind the substeps only.  Loaded there, each is a memory round trip with nothing to overlap; loaded here they
-  // share the state's.  They wait in two words of LDS, not in registers the solver would have to carry (read back through an opaque copy
-  // of the lane's index: the compiler must not forward the stored values to the loads, which would keep them in VGPRs after all).
-  __shared__ unsigned tail_park[2 * 64];
-  const int t_in = s.t[i]; const unsigned ep_in = s.episode[i];
-  float q[S::NV], v[S::NV], ctrl[S::NU], xi[S::NXI];
-  static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (s.qpos + (size_t)k * B)[i]; v[k] = (s.qvel + (size_t)k * B)[i]; });
-  static_for<0, S::NU>([&](auto KK) { constexpr int k = KK; ctrl[k] = (action + (size_t)k * B)[i]; });
-  static_for<0, S::NXI>([&](auto KK) { constexpr int k = KK; xi[k] = (s.xi + (size_t)k * B)[i]; });
-  tail_park[threadIdx.x] = (unsigned)t_in; tail_park[64 + threadIdx.x] = ep_in;
-  PlanarGeom<float, S> G; load_geom<S>(s, i, ugeom, G);
-  LaneParams<float, S> P; lane_params(S{}, xi, P);
-  // the dynamics are invariant to the root x translation: integrate the step from x = 0 so the
-  // forward-progress reward (posafter - posbefore)/dt keeps full fp32 resolution far from the origin
-#if defined(REX_KTIME) || defined(REX_WAVETIME)
-  unsigned long long tk0 = __builtin_amdgcn_s_memtime();
-#endif
-  const float x_before = q[0];
-  q[0] = 0.0f;
-  bool capped = false;
-  float acc[S::NV];
-  static_for<0, S::NV>([&](auto KK) { acc[KK] = 0.0f; });
-  // which code the general solver modes run: the LIST solver in the two-lanes-per-env kernels (per-unit data in a column of LDS, one column per
-  // lane: 9 - 20 KB per wave), the rolled row list in the hopper's two-waves-per-SIMD kernel, the unrolled per-slot instantiations otherwise
-  constexpr int GEN = PAIR ? 2 : (ROLLED ? 1 : 0);
-  float* slot_col = nullptr;
-  if constexpr (GEN == 2) {
-    __shared__ float slot_lds[SlotMem<float, S, PAIR>::WORDS];
-    slot_col = slot_lds + threadIdx.x;
-  }
-#pragma unroll 1
-  for (int f = 0; f < S::FRAME_SKIP; f++) capped |= substep<float, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, f > 0, slot_col);   // do_simulation, jinja_mujoco_env.py:170-173
-  if (PAIR && (threadIdx.x & 1u)) return;   // the even lane of a pair writes the results and runs the fused reset
-  // the output addresses are formed from an opaque copy of the lane index: formed from `i`, the compiler computes all of them
-  // next to the loads at the top, carries them through the solver, spills them and reloads each with a wait of its own
-  unsigned io = i; asm volatile("" : "+v"(io));
-#if defined(REX_KTIME)
-  if ((threadIdx.x & 63) == 0) atomicAdd(&g_ktime[5], __builtin_amdgcn_s_memtime() - tk0);
-#endif
-#if defined(REX_WAVETIME)
-  const unsigned long long tk1 = __builtin_amdgcn_s_memtime();
-  if ((threadIdx.x & 63) == 0) g_wavetime[blockIdx.x & 8191] = tk1 - tk0;
-#endif
-  const float dx = q[0];
-  q[0] = x_before + dx;
-  // reward / done
-  float asq = 0.0f;
-  static_for<0, S::NU>([&](auto KK) { asq += ctrl[KK] * ctrl[KK]; });
-  const float dt = float(S::TIMESTEP * S::FRAME_SKIP);
-  float r = dx / dt + S::ALIVE - S::CTRL_COST * asq;
-  bool finite = true;
-  static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; finite = finite && isfinite(q[k]) && isfinite(v[k]); });
-  bool dn = false;
-  if constexpr (S::KIND == 1) {          // random_hopper.py:92
-    bool small = true;
-    static_for<2, S::NV>([&](auto KK) { constexpr int k = KK; small = small && fabsf(q[k]) < 100.0f; });
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; small = small && fabsf(v[k]) < 100.0f; });
-    dn = !(finite && small && q[1] > 0.7f && fabsf(q[2]) < 0.2f);
-  } else if constexpr (S::KIND == 3) {   // random_walker2d.py:124-125
-    dn = !(q[1] > 0.8f && q[1] < 2.0f && q[2] > -1.0f && q[2] < 1.0f);
-  } else {                               // random_half_cheetah.py:108
-    dn = false;
-  }
-  if (fl.endless) dn = false;            // random_hopper.py:95-96
-  if (!fl.readonly) {   // (rex_replay: nothing of the handle is written, its counters included)
-    if (!finite) atomicAdd(s.counters + 0, 1ull);
-    if (capped && threadIdx.x == 0) atomicAdd(s.counters + 2, 1ull);
-  }
-  unsigned lo = threadIdx.x; asm volatile("" : "+v"(lo));
-  const unsigned ep_prev = tail_park[64 + lo];
-  int t = (int)tail_park[lo] + 1;
-#if defined(REX_WAVETIME)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long tt0 = __builtin_amdgcn_s_memtime();
-#endif
-  bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;     // gym TimeLimit
-  bool d = dn || trunc;
-  const unsigned long long subseq = (unsigned long long)(s.env_offset + io);
-  float ob[S::NOBS];
-  obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq,
-                (unsigned long long)ep_prev * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE);
-  // what always carries the STEPPED values goes out first
-  if (term_obs) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (term_obs + (size_t)k * B)[io] = ob[k]; });
-  reward[io] = r; done_out[io] = d ? 1 : 0;
-  if (trunc_out) trunc_out[io] = trunc ? 1 : 0;
-  if (fl.info) { fl.info[io] = dx / dt; (fl.info + (size_t)B)[io] = -S::CTRL_COST * asq; }   // info: reward_run, reward_ctrl (random_half_cheetah.py:105-110)
-#if defined(REX_WAVETIME)
-  const unsigned long long tr0 = __builtin_amdgcn_s_memtime();
-#endif
-  // Auto-reset fused into the step launch (saves the masked reset launch and the kernel boundary).  A finished lane's state, t, done and
-  // observation are REPLACED in registers by those of its next episode before anything is stored: every row is written once, by one
-  // set of stores for the whole wave, and nothing in the tail waits for memory (t and episode came with the state; gfx950 counts loads
-  // and stores in one counter, so a load waited for here would drain every store issued before it).
-  unsigned char dflag = d ? 2 : 0;
-  if (fused_reset && d) {
-    const unsigned ep = ep_prev + 1; s.episode[io] = ep;
-#if defined(REX_WAVETIME)
-    atomicMax(&g_wavetail[blockIdx.x & 8191][2], __builtin_amdgcn_s_memtime() - tr0);
-#endif
-#if defined(REX_DIAG_CHEAP_RESET)   // timing diagnostics only: what the RNG work of the fused reset costs the step kernel
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (k == 1 && S::KIND != 2) ? 1.25f : 0.0f; v[k] = 0.0f; });
-    t = 0; dflag = 0;
-#else
-    reset_state_values<S>(s.seed, subseq, ep, q, v);
-    t = 0; dflag = 0;
-    obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + STEP_BASE);
-#if defined(REX_WAVETIME)
-    atomicMax(&g_wavetail[blockIdx.x & 8191][3], __builtin_amdgcn_s_memtime() - tr0);
-#endif
-    if ((resample & RS_RESAMPLE) && dr.type != REX_DR_NONE) {
-      // separate stream region so the xi draw does not depend on the state draws.  truncnorm / gaussian consume a data-dependent number
-      // of words (redraw rules) and fullgaussian replays the stream per dimension: they take their words from PhiloxWords
-      if (dr.type == REX_DR_UNIFORM && dr.dim <= S::NXI) sample_task_uniform<S::NXI>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io);
-      else sample_task<PhiloxWords>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io, s.counters);
-    }
-#if defined(REX_WAVETIME)
-    atomicMax(&g_wavetail[blockIdx.x & 8191][4], __builtin_amdgcn_s_memtime() - tr0);
-#endif
-    if constexpr (S::KIND == 3) {   // (reads the new xi lengths back behind their stores)
-      if (resample & RS_DERIVE) {
-        if constexpr (PAIR) walker_derive_lane(s, io, (resample & RS_REFRESH) ? 1 : 0);
-        else walker_derive_call(s, io, (resample & RS_REFRESH) ? 1 : 0);   // (one lane per env: inlined it spills the step's own state; as a call only this branch pays)
-      }
-    }
-#endif
-#if defined(REX_WAVETIME)
-    atomicMax(&g_wavetail[blockIdx.x & 8191][5], __builtin_amdgcn_s_memtime() - tr0);
-#endif
-  }
-  if (!fl.readonly) {
-    s.t[io] = t;
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[io] = q[k]; (s.qvel + (size_t)k * B)[io] = v[k]; });
-    s.done[io] = dflag;
-  }
-  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (obs + (size_t)k * B)[io] = ob[k]; });
-#if defined(REX_WAVETIME)
-  if ((threadIdx.x & 63) == 0) { g_waveinfo[blockIdx.x & 8191][1] += __builtin_amdgcn_s_memtime() - tr0; }   // slot 1 ("iters", unused): cycles in the fused reset
-  if ((threadIdx.x & 63) == 0) { unsigned long long* ph = g_wavephase[blockIdx.x & 8191]; ph[0] = tk0 - tp0; ph[1] = tk1 - tk0; ph[2] = tr0 - tk1; ph[3] = __builtin_amdgcn_s_memtime() - tr0; }
-  if ((threadIdx.x & 63) == 0) { unsigned long long* tl = g_wavetail[blockIdx.x & 8191]; tl[0] = tt0 - tk1; tl[1] = tr0 - tk1; }
-  if ((threadIdx.x & 63) == 0) { unsigned long long* pl = g_waveplace[blockIdx.x & 8191]; pl[0] = tw0; pl[1] = __builtin_amdgcn_s_memrealtime();
-    pl[2] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4); pl[3] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20); }   // HW_REG_HW_ID, HW_REG_XCC_ID
-#endif
-}
-
-// reset_model (random_hopper.py:112-120, random_half_cheetah.py:123-131, random_walker2d.py:144-153)
-// + set_random_task (random_env.py:37-39) for one lane.
-template <class S>
-__device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepFlags& fl, const DRParams& dr, int resample,
-                                                  int reset_state, unsigned i, float* __restrict__ obs) {
-  const long long B = s.B;
-  unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
-#if defined(REX_DIAG_CHEAP_RESET)   // timing diagnostics only: what the RNG work of the fused reset costs the step kernel
-  if (reset_state) {
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = (k == 1 && S::KIND != 2) ? 1.25f : 0.0f; (s.qvel + (size_t)k * B)[i] = 0.0f; });
-    s.t[i] = 0; s.done[i] = 0;
-  }
-  return;
-#endif
-  if (reset_state) {
-    rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
-    float q[S::NV], v[S::NV];
-    const float c = S::INIT_NOISE;
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK;
-      q[k] = c * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);            // init_qpos + U(-c, c)
-      if constexpr (S::KIND == 2) v[k] = 0.1f * rocrand_normal(&st);       // random_half_cheetah.py:125
-      else v[k] = c * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-    });
-    if constexpr (S::KIND != 2) q[1] += 1.25f;                             // init_qpos[1] = 1.25 (ref, hopper.xml:30)
-    static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = q[k]; (s.qvel + (size_t)k * B)[i] = v[k]; });
-    s.t[i] = 0; s.done[i] = 0;
-    if (obs) {
-      rocrand_state_philox4x32_10 st2;
-      if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
-      write_obs<S>(q, v, obs, B, i, fl.noisy != 0, fl.noise_std, &st2);
-    }
-  }
-  if (resample && dr.type != REX_DR_NONE) {
-    // separate stream region so the xi draw does not depend on reset_state
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, i, s.counters);
-  }
-}
-
-// pending_bit: walker2d's auto-reset under DR -- the lane's geometry has to follow its NEW xi lengths, which is the derive
-// launch behind this one; the auto-reset mask is s.done itself and reset_lane clears it, so the reset leaves this bit for
-// walker_derive_kernel to find (and clear).
-template <class S>
-__global__ void __launch_bounds__(64) planar_reset_kernel(DevState s, StepFlags fl, DRParams dr, int resample, int reset_state,
-                                                          const unsigned char* __restrict__ mask, int mask_bit,
-                                                          float* __restrict__ obs, int pending_bit) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.B) return;
-  if (mask && !(mask[i] & mask_bit)) return;
-  planar_reset_lane<S>(s, fl, dr, resample, reset_state, i, obs);
-  if (pending_bit) s.done[i] = (unsigned char)pending_bit;
-}
-
-#if REX_EN_WALKER2D
-// walker2d: re-derive the per-env model constants from the xi lengths for the masked lanes
-// (replaces build_model() inside RandomWalker2dEnv.set_task, random_walker2d.py:106-113).
-__global__ void __launch_bounds__(64) walker_derive_kernel(DevState s, const unsigned char* mask, int mask_bit,
-                                                           int refresh_frozen_masses, int clear_pending) {
-  using S = Walker2dSpec;
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;
-  if (mask && !(mask[i] & mask_bit)) return;
-  if (clear_pending) s.done[i] = 0;   // (mask is s.done: the pending bit planar_reset_kernel left)
-  walker_derive_lane(s, i, refresh_frozen_masses);
-}
-__device__ __forceinline__ void walker_derive_lane(const DevState& s, unsigned i, int refresh_frozen_masses) {
-  using S = Walker2dSpec;
-  double size[4];
-  for (int k = 0; k < 4; k++) size[k] = (double)s.xi[(long long)(7 + k) * s.B + i];
-  PlanarGeom<double, S> G; SolParams<double> sp; double nominal[S::NB];
-  derive_model<double, S>(size, G, nominal, sp);
-  double c[kWalkerCompact];
-  walker_compact_from_geom(G, c);
-  for (int k = 0; k < kWalkerCompact; k++) (s.geom + (size_t)k * s.B)[i] = (float)c[k];
-  // RandomWalker2dUnmodeled.set_task rebuilds the model and rewrites body_mass[4:] only, so the frozen
-  // masses 1..3 become the geometry-derived ones of the new lengths (random_walker2d_unmodeled.py:109-116)
-  if (refresh_frozen_masses) for (int b = 0; b < 3; b++) (s.xi + (size_t)b * s.B)[i] = (float)nominal[b];
-}
-__device__ __attribute__((noinline)) void walker_derive_call(const DevState& s, unsigned i, int refresh_frozen_masses) { walker_derive_lane(s, i, refresh_frozen_masses); }
-#else
-__device__ __forceinline__ void walker_derive_lane(const DevState&, unsigned, int) {}
-__device__ __forceinline__ void walker_derive_call(const DevState&, unsigned, int) {}
-
-#endif
-
-template <class S>
-__global__ void __launch_bounds__(64) planar_obs_kernel(DevState s, float* __restrict__ obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;
-  float q[S::NV], v[S::NV];
-  static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (s.qpos + (size_t)k * s.B)[i]; v[k] = (s.qvel + (size_t)k * s.B)[i]; });
-  write_obs<S>(q, v, obs, s.B, i, false, 0.0f, nullptr);
-}
-__global__ void __launch_bounds__(64) cartpole_obs_kernel(DevState s, float* __restrict__ obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;   // 32-bit lane offset + uniform (SGPR) row bases
-  if (i >= s.B) return;
-  const long long B = s.B;
-  obs[i] = s.qpos[i]; obs[B + i] = s.qvel[i]; obs[2 * B + i] = s.qpos[B + i]; obs[3 * B + i] = s.qvel[B + i];
-}
 __global__ void fill_rows_kernel(float* dst, const float* vals, int nrows, long long B) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   for (int k = 0; k < nrows; k++) dst[(long long)k * B + i] = vals[k];
 }
-
-// ------------------------------------------------------------------------------------------
-// Humanoid (random_envs/jinja/random_humanoid.py).  One env per lane; the per-lane working set of a
-// forward evaluation (hum::Scratch, ~20 KB: M 23x23, J and M^-1 J^T for up to 64 rows, contact list)
-// lives in HIP scratch memory, lane-interleaved so every access of a wave is one coalesced segment.
-// The compiled model is uniform and sits in __constant__ memory.
-// ------------------------------------------------------------------------------------------
-#if REX_EN_HUMANOID
-__constant__ hum::Model<float> c_hum;
-
-__device__ __forceinline__ void hum_lane(const DevState& s, unsigned i, hum::Lane<float>& L) {
-  // set_task (random_humanoid.py:156-158): body_mass[1:] = xi[:13]; dof_damping[6:] = xi[13:]
-  L.mass[0] = 0.0f;
-  for (int k = 0; k < 13; k++) L.mass[1 + k] = (s.xi + (size_t)k * s.B)[i];
-  for (int d = 0; d < 6; d++) L.damping[d] = 0.0f;
-  for (int k = 0; k < 17; k++) L.damping[6 + k] = (s.xi + (size_t)(13 + k) * s.B)[i];
-}
-
-__global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags fl, const float* __restrict__ action,
-                                                           float* __restrict__ obs, float* __restrict__ reward,
-                                                           unsigned char* __restrict__ done_out, unsigned char* __restrict__ trunc_out,
-                                                           float* __restrict__ term_obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.B) return;
-  const size_t B = (size_t)s.B;
-  hum::Lane<float> L; hum_lane(s, i, L);
-  float q[hum::NQ], v[hum::NV], a[hum::NU], xp[hum::NBODY];
-  for (int k = 0; k < hum::NQ; k++) q[k] = (s.qpos + k * B)[i];
-  for (int k = 0; k < hum::NV; k++) v[k] = (s.qvel + k * B)[i];
-  for (int k = 0; k < hum::NU; k++) a[k] = (action + k * B)[i];
-  for (int b = 0; b < hum::NBODY; b++) xp[b] = (s.aux + b * B)[i];
-  hum::Kin<float> kn; hum::Scratch<float> sc;
-#if defined(REX_KTIME)
-  for (int k = 0; k < HT_SLOTS; k++) kn.tacc[k] = 0;
-#endif
-  float r; bool dn;
-  rocrand_state_philox4x32_10 st;
-  int t = s.t[i] + 1;
-  if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i),
-                             (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, &st);
-#if defined(REX_WAVETIME)
-  const unsigned long long tk0 = __builtin_amdgcn_s_memtime();
-#endif
-  float terms[4];
-  hum::env_step(c_hum, L, q, v, a, xp, kn, sc, r, dn, [&](int k, float val) {
-    // noise only on the qpos / qvel slices (random_humanoid.py:193-204)
-    if (fl.noisy && k < 45) val += fl.noise_std * rocrand_normal(&st);
-    (obs + k * B)[i] = val;
-    if (term_obs) (term_obs + k * B)[i] = val;
-  }, terms);
-  if (fl.info) for (int k = 0; k < 4; k++) (fl.info + k * B)[i] = terms[k];   // reward_linvel, _quadctrl, _alive, _impact (random_humanoid.py:182-187)
-#if defined(REX_WAVETIME)
-  if ((threadIdx.x & 63) == 0) g_wavetime[blockIdx.x & 8191] = __builtin_amdgcn_s_memtime() - tk0;
-#endif
-#if defined(REX_KTIME)
-  for (int k = 0; k < HT_SLOTS; k++) {   // one flush per wave and kernel: the wave maximum of every accumulator
-    unsigned long long v = kn.tacc[k];
-    for (int off = 32; off > 0; off >>= 1) { unsigned long long o = __shfl_xor(v, off); v = o > v ? o : v; }
-    if ((threadIdx.x & 63) == 0) atomicAdd(&g_ktime[8 + k], v);
-#if defined(REX_WAVETIME)
-    if ((threadIdx.x & 63) == 0 && k < 16) g_wavehum[blockIdx.x & 1023][k] = v;
-#endif
-  }
-#endif
-  bool finite = true;
-  for (int k = 0; k < hum::NQ; k++) finite = finite && isfinite(q[k]);
-  for (int k = 0; k < hum::NV; k++) finite = finite && isfinite(v[k]);
-  if (!finite) dn = true;                                           // a diverged lane ends its episode
-  if (fl.endless && finite) dn = false;
-  bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;
-  bool d = dn || trunc;
-  if (!fl.readonly) {   // (rex_replay: nothing of the handle is written, its counters included)
-    if (!finite) atomicAdd(s.counters + 0, 1ull);
-    if (kn.overflow) atomicAdd(s.counters + 3, 1ull);
-    s.t[i] = t;
-    for (int k = 0; k < hum::NQ; k++) (s.qpos + k * B)[i] = q[k];
-    for (int k = 0; k < hum::NV; k++) (s.qvel + k * B)[i] = v[k];
-    for (int b = 0; b < hum::NBODY; b++) (s.aux + b * B)[i] = xp[b];
-    s.done[i] = d ? 2 : 0;
-  }
-  reward[i] = r; done_out[i] = d ? 1 : 0;
-  if (trunc_out) trunc_out[i] = trunc ? 1 : 0;
-}
-
-// ---- the step kernel over TWO LANES PER ENVIRONMENT (humanoid_pair.hpp): lanes 2e / 2e + 1 of a 64-lane block hold env e, the right
-// lane the trunk + right leg / arm, the left lane the trunk (replicated) + left leg / arm; 32 envs per wave, every lane active.
-struct DevPair {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __device__ __forceinline__ int side() const { return (int)(threadIdx.x & 1u); }
-  __device__ __forceinline__ float xchg(float x) const { return pair_xchg(x); }
-  __device__ __forceinline__ unsigned xchg(unsigned x) const { return pair_xchg(x); }
-  __device__ __forceinline__ bool any(bool b) const { return REX_WAVE_ANY(b); }
-  __device__ __forceinline__ float* col() const { return hum::hum_lds + (threadIdx.x >> 1) * hum::pr::PAIR_WORDS; }
-  // LDS hand-over between the two lanes of a pair: same wave, LDS operations of a wave execute in order, so only the COMPILER has
-  // to be kept from moving a read of the partner's words above the partner's (= this instruction's) write
-  __device__ __forceinline__ void sync() const {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-#else   // (the host pass only parses the kernel body)
-  __device__ int side() const { return 0; }
-  __device__ float xchg(float x) const { return x; }
-  __device__ unsigned xchg(unsigned x) const { return x; }
-  __device__ bool any(bool b) const { return b; }
-  __device__ float* col() const { return nullptr; }
-  __device__ void sync() const {}
-#endif
-};
-
-__global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, StepFlags fl, const float* __restrict__ action,
-                                                                float* __restrict__ obs, float* __restrict__ reward,
-                                                                unsigned char* __restrict__ done_out, unsigned char* __restrict__ trunc_out,
-                                                                float* __restrict__ term_obs, DRParams dr, int fused_reset, int resample) {
-  namespace pr = hum::pr;
-  const unsigned lane = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned i = lane >> 1;
-  if (i >= s.B) return;   // (both lanes of a pair leave together)
-  const bool left = (lane & 1u) != 0u;
-  const size_t B = (size_t)s.B;
-  const DevPair p;
-  // set_task (random_humanoid.py:156-158): body_mass[1:] = xi[:13]; dof_damping[6:] = xi[13:] -- this lane's 8 bodies / 16 dofs
-  pr::PLane<float> L;
-  static_for<0, pr::LB>([&](auto BB) { constexpr int lb = BB; L.mass[lb] = (s.xi + (size_t)((left ? pr::gbL(lb) : pr::gbR(lb)) - 1) * B)[i]; });
-  static_for<0, pr::LD>([&](auto DD) { constexpr int ld = DD;
-    if constexpr (ld < 6) L.damping[ld] = 0.0f; else L.damping[ld] = (s.xi + (size_t)(13 + (left ? pr::gdL(ld) : pr::gdR(ld)) - 6) * B)[i]; });
-  float ql[pr::LQ], vl[pr::LD], cl[pr::LU], xp[pr::LB];
-  static_for<0, 7>([&](auto KK) { constexpr int k = KK; ql[k] = (s.qpos + (size_t)k * B)[i]; });
-  static_for<6, pr::LD>([&](auto DD) { constexpr int ld = DD; ql[ld + 1] = (s.qpos + (size_t)((left ? pr::gdL(ld) : pr::gdR(ld)) + 1) * B)[i]; });
-  static_for<0, pr::LD>([&](auto DD) { constexpr int ld = DD; vl[ld] = (s.qvel + (size_t)(left ? pr::gdL(ld) : pr::gdR(ld)) * B)[i]; });
-  static_for<6, pr::LD>([&](auto DD) { constexpr int ld = DD;     // data.ctrl holds the raw action (:167); motor u drives dof kActDof[u]
-    constexpr int uR = ld == 6 ? 1 : ld == 7 ? 0 : ld == 8 ? 2 : ld < 13 ? 3 + (ld - 9) : 11 + (ld - 13);
-    constexpr int uL = ld < 9 ? uR : ld < 13 ? 7 + (ld - 9) : 14 + (ld - 13);
-    cl[ld - 6] = (action + (size_t)(left ? uL : uR) * B)[i]; });
-  static_for<0, pr::LB>([&](auto BB) { constexpr int lb = BB; xp[lb] = (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i]; });
-  float asq_side = 0.0f, asq = 0.0f;
-  static_for<0, 3>([&](auto KK) { asq += cl[KK] * cl[KK]; });
-  static_for<3, pr::LU>([&](auto KK) { asq_side += cl[KK] * cl[KK]; });
-  asq += pr::psum(p, asq_side);
-  pr::PKin<float> kn; pr::PScratch<float> sc; pr::PObs<float> park;
-#if defined(REX_KTIME)
-  for (int k = 0; k < HT_SLOTS; k++) kn.tacc[k] = 0;
-#endif
-  const int t = s.t[i] + 1;
-#if defined(REX_WAVETIME)
-  const unsigned long long tk0 = __builtin_amdgcn_s_memtime();
-#endif
-  float r, terms[4]; bool dn;
-  pr::env_step(p, c_hum, L, ql, vl, cl, asq, xp, kn, sc, park, r, dn, terms);
-#if defined(REX_WAVETIME)
-  if ((threadIdx.x & 63) == 0) g_wavetime[blockIdx.x & 8191] = __builtin_amdgcn_s_memtime() - tk0;
-#endif
-#if defined(REX_KTIME)
-  for (int k = 0; k < HT_SLOTS; k++) {   // one flush per wave and kernel: the wave maximum of every accumulator
-    unsigned long long v = kn.tacc[k];
-    for (int off = 32; off > 0; off >>= 1) { unsigned long long o = __shfl_xor(v, off); v = o > v ? o : v; }
-    if ((threadIdx.x & 63) == 0) atomicAdd(&g_ktime[8 + k], v);
-#if defined(REX_WAVETIME)
-    if ((threadIdx.x & 63) == 0 && k < 16) g_wavehum[blockIdx.x & 1023][k] = v;
-#endif
-  }
-#endif
-  // observation (random_humanoid.py:193-204); noise only on the qpos / qvel slices: the 45 draws in row order, as one lane per env made them
-  float nz[45];
-  if (fl.noisy) {
-    rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, &st);
-    for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st);
-  }
-  pr::emit_obs(p, ql, vl, park, [&](auto RR, auto RL, float val) {
-    constexpr int rr = RR, rl = RL;
-    if constexpr (rr < 45 && rl < 45) { if (fl.noisy) val += left ? nz[rl] : nz[rr]; }
-    const size_t row = left ? (size_t)rl : (size_t)rr;
-    (obs + row * B)[i] = val;
-    if (term_obs) (term_obs + row * B)[i] = val;
-  });
-  bool finite = true;
-  static_for<0, pr::LQ>([&](auto KK) { finite = finite && isfinite(ql[KK]); });
-  static_for<0, pr::LD>([&](auto KK) { finite = finite && isfinite(vl[KK]); });
-  finite = finite && (p.xchg(finite ? 1u : 0u) != 0u);
-  if (!finite) dn = true;                                           // a diverged lane ends its episode
-  if (fl.endless && finite) dn = false;
-  const bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;
-  const bool d = dn || trunc;
-  if (!fl.readonly) {   // (rex_replay: nothing of the handle is written, its counters included)
-    static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD; const size_t g = left ? pr::gdL(ld) : pr::gdR(ld);
-      (s.qpos + (g + 1) * B)[i] = ql[ld + 1]; (s.qvel + g * B)[i] = vl[ld]; });
-    static_for<3, pr::LB>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i] = xp[lb]; });
-  }
-  if (!left) {
-    if (!fl.readonly) {
-      if (!finite) atomicAdd(s.counters + 0, 1ull);
-      if (kn.overflow) atomicAdd(s.counters + 3, 1ull);
-      s.t[i] = t;
-      static_for<0, 10>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = ql[k]; });
-      static_for<0, 9>([&](auto KK) { constexpr int k = KK; (s.qvel + (size_t)k * B)[i] = vl[k]; });
-      static_for<0, 3>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(lb + 1) * B)[i] = xp[lb]; });
-      s.aux[i] = 0.0f;                                                // world body
-      s.done[i] = d ? 2 : 0;
-    }
-    if (fl.info) for (int k = 0; k < 4; k++) (fl.info + k * B)[i] = terms[k];   // reward_linvel, _quadctrl, _alive, _impact (random_humanoid.py:182-187)
-    reward[i] = r; done_out[i] = d ? 1 : 0;
-    if (trunc_out) trunc_out[i] = trunc ? 1 : 0;
-  }
-  // Auto-reset fused into the step launch (the masked reset launch behind every step was 80 us of a 1.77 ms step): a finished env
-  // restarts here, both lanes of its pair.  reset_model (random_humanoid.py:219-234) exactly as humanoid_reset_kernel does it -- the same
-  // Philox streams and draw order (q 0..23, then v 0..22), set_state -> sim.forward() with the masses in force, THEN
-  // set_random_task -- with the forward's kinematics / com / velocities over the pair's local trees.
-  if (fused_reset && d) {
-    const unsigned ep = s.episode[i] + 1;
-    rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
-    static_for<0, hum::NQ>([&](auto KK) { constexpr int k = KK;
-      const float val = c_hum.qpos0[k] + 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-      if constexpr (k < 10) ql[k] = val;                              // free joint + the three abdomen hinges: replicated
-      else static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD;
-        if constexpr (pr::gdR(ld) + 1 == k) ql[ld + 1] = left ? ql[ld + 1] : val;
-        if constexpr (pr::gdL(ld) + 1 == k) ql[ld + 1] = left ? val : ql[ld + 1]; }); });
-    static_for<0, hum::NV>([&](auto KK) { constexpr int k = KK;
-      const float val = 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-      if constexpr (k < 9) vl[k] = val;
-      else static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD;
-        if constexpr (pr::gdR(ld) == k) vl[ld] = left ? vl[ld] : val;
-        if constexpr (pr::gdL(ld) == k) vl[ld] = left ? val : vl[ld]; }); });
-    {
-      pr::PSmooth<float> S;
-      pr::kinematics(p, c_hum, ql, S);
-      pr::com_pos(p, c_hum, L, S);
-      float qb[pr::LD];
-      pr::com_vel_rne(p, c_hum, vl, S, qb);
-      static_for<0, pr::LB>([&](auto BB) { constexpr int b = BB; for (int k = 0; k < 10; k++) park.cinert[b][k] = S.cinert[b][k]; for (int k = 0; k < 6; k++) park.cvel[b][k] = S.cvel[b][k]; xp[b] = S.xipos[b][0]; });
-      static_for<0, pr::LD>([&](auto II) { park.act[II] = 0.0f; });     // sim.reset() zeroes data.ctrl
-    }
-    if (fl.noisy) {
-      rocrand_state_philox4x32_10 st2;
-      rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
-      for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st2);
-    }
-    pr::emit_obs(p, ql, vl, park, [&](auto RR, auto RL, float val) {
-      constexpr int rr = RR, rl = RL;
-      if constexpr (rr < 45 && rl < 45) { if (fl.noisy) val += left ? nz[rl] : nz[rr]; }
-      (obs + (left ? (size_t)rl : (size_t)rr) * B)[i] = val;
-    });
-    static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD; const size_t g = left ? pr::gdL(ld) : pr::gdR(ld);
-      (s.qpos + (g + 1) * B)[i] = ql[ld + 1]; (s.qvel + g * B)[i] = vl[ld]; });
-    static_for<3, pr::LB>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i] = xp[lb]; });
-    if (!left) {
-      s.episode[i] = ep;
-      static_for<0, 10>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = ql[k]; });
-      static_for<0, 9>([&](auto KK) { constexpr int k = KK; (s.qvel + (size_t)k * B)[i] = vl[k]; });
-      static_for<0, 3>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(lb + 1) * B)[i] = xp[lb]; });
-      s.t[i] = 0; s.done[i] = 0;
-      if (resample && dr.type != REX_DR_NONE)
-        sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, B, i, s.counters);
-    }
-  }
-}
-
-// reset_model (random_humanoid.py:219-234): init noise U(-.01,.01) on all of qpos (incl. the quaternion) and qvel,
-// set_state -> sim.forward() with the CURRENT task, THEN set_random_task (the cinert block of the
-// returned observation is computed with the previous episode's masses).
-__global__ void __launch_bounds__(64) humanoid_reset_kernel(DevState s, StepFlags fl, DRParams dr, int resample, int reset_state,
-                                                            const unsigned char* __restrict__ mask, int mask_bit,
-                                                            float* __restrict__ obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.B) return;
-  if (mask && !(mask[i] & mask_bit)) return;
-  const size_t B = (size_t)s.B;
-  unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
-  rocrand_state_philox4x32_10 st;
-  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
-  if (reset_state) {
-    float q[hum::NQ], v[hum::NV], xp[hum::NBODY];
-    for (int k = 0; k < hum::NQ; k++) q[k] = c_hum.qpos0[k] + 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-    for (int k = 0; k < hum::NV; k++) v[k] = 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-    hum::Lane<float> L; hum_lane(s, i, L);
-    hum::Kin<float> kn; hum::Scratch<float> sc;
-    rocrand_state_philox4x32_10 st2;
-    if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
-    hum::env_reset_obs(c_hum, L, q, v, xp, kn, sc, [&](int k, float val) {
-      if (fl.noisy && k < 45) val += fl.noise_std * rocrand_normal(&st2);
-      if (obs) (obs + k * B)[i] = val;
-    });
-    for (int k = 0; k < hum::NQ; k++) (s.qpos + k * B)[i] = q[k];
-    for (int k = 0; k < hum::NV; k++) (s.qvel + k * B)[i] = v[k];
-    for (int b = 0; b < hum::NBODY; b++) (s.aux + b * B)[i] = xp[b];
-    s.t[i] = 0; s.done[i] = 0;
-  }
-  if (resample && dr.type != REX_DR_NONE) {
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, B, i, s.counters);
-  }
-}
-
-// set_state / get_obs: sim.forward() at the stored state (jinja_mujoco_env.py:146-154)
-__global__ void __launch_bounds__(64) humanoid_forward_kernel(DevState s, float* __restrict__ obs) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.B) return;
-  const size_t B = (size_t)s.B;
-  float q[hum::NQ], v[hum::NV], xp[hum::NBODY];
-  for (int k = 0; k < hum::NQ; k++) q[k] = (s.qpos + k * B)[i];
-  for (int k = 0; k < hum::NV; k++) v[k] = (s.qvel + k * B)[i];
-  hum::Lane<float> L; hum_lane(s, i, L);
-  hum::Kin<float> kn; hum::Scratch<float> sc;
-  hum::env_reset_obs(c_hum, L, q, v, xp, kn, sc, [&](int k, float val) { if (obs) (obs + k * B)[i] = val; });
-  for (int b = 0; b < hum::NBODY; b++) (s.aux + b * B)[i] = xp[b];
-}
-
-#endif  // REX_EN_HUMANOID
 
 // ------------------------------------------------------------------------------------------
 // host-side handle
@@ -2138,3 +1193,4 @@ extern "C" int rex_rollout_read_bad_indices(rex_t* h, int64_t* out, int clear) {
   if (clear) HIP_TRY(hipMemset(rollout_bad(h), 0, sizeof v));
   return REX_OK;
 }
+

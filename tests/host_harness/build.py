@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SO = os.path.join(HERE, "_build_planar_host.so")
 SRC = os.path.join(HERE, "planar_host.cpp")
 DEPS = [SRC] + [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in
-                ("planar_spec.hpp", "planar_engine.hpp", "planar_model.hpp")]
+                ("planar_spec.hpp", "planar_engine.hpp", "planar_model.hpp", "probes.hpp")]
 _D = ctypes.POINTER(ctypes.c_double)
 _lib = None
 KINDS = {"hopper": 1, "halfcheetah": 2, "walker2d": 3}

@@ -1,4 +1,5 @@
 """The C-ABI library loads and exports every symbol include/rex.h declares (no compute calls)."""
+import glob
 import os
 import re
 
@@ -45,7 +46,8 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------- source-level contracts of the C-ABI
-_SRC = os.path.join(ROOT, "random-envs_amd", "csrc", "rex_hip.hip")
+_CSRC = os.path.join(ROOT, "random-envs_amd", "csrc")
+_SRC = os.path.join(_CSRC, "rex_hip.hip")
 _DEVICE_WORK = re.compile(r"hipLaunchKernelGGL|hipMemcpy|hipMemset|hipDeviceSynchronize|hipEvent(Record|Create|Synchronize)|hipMalloc|hipFree|"
                           r"\bcopy_rows\(|\bdo_reset\(|\blaunch_[a-z_]+(<[A-Za-z0-9_]+>)?\(|\bensure_replay_scratch\(")
 
@@ -89,8 +91,10 @@ def test_the_product_reads_no_environment_variable_outside_the_gated_knobs():
     (honoured only beside REX_ALLOW_TUNING=1, refused by rex_create otherwise), the physics-changing diagnostics are compiled in by -DREX_TUNING
     only, and build() never defines it."""
     src = open(_SRC).read()
-    for inc in ("planar_engine.hpp", "planar_model.hpp", "planar_spec.hpp", "humanoid_engine.hpp", "humanoid_pair.hpp", "humanoid_model.hpp"):
-        assert "getenv" not in open(os.path.join(ROOT, "random-envs_amd", "csrc", inc)).read(), inc
+    headers = glob.glob(os.path.join(_CSRC, "*.hpp"))
+    assert len(headers) >= 6
+    for inc in headers:
+        assert "getenv" not in open(inc).read(), inc
     lines = [l for l in src.splitlines() if "getenv(" in l and not l.lstrip().startswith("//")]
     allowed = ('getenv("REX_ALLOW_TUNING")', "if (getenv(k)) return k", "getenv(name)", 'getenv("REX_DIAG_NOCONTACT") || getenv("REX_HUM_ITERS")')
     stray = [l.strip() for l in lines if not any(a in l for a in allowed)]
@@ -101,6 +105,25 @@ def test_the_product_reads_no_environment_variable_outside_the_gated_knobs():
             assert before.rfind("#if defined(REX_TUNING)") > before.rfind("#endif"), name
     import __graft_entry__ as g
     assert not any("REX_TUNING" in f for f in g.HIPCC_FLAGS)
+
+
+def test_probe_switches_live_in_probes_hpp_and_dead_switches_are_gone():
+    """A reader sees the product kernels without preprocessing them in their head: the profiling switches are tested in csrc/probes.hpp only
+    (its hooks are empty in the product build), and the diagnostic switches that no test, script or document could reach stay deleted."""
+    probe_switches = ("REX_KTIME", "REX_WAVETIME", "REX_KSTATS", "REX_PHASES", "REX_NOPHASES", "REX_STATS", "REX_MARKS")
+    deleted = ("REX_DIAG_CHEAP_RESET", "REX_DIAG_MAXIT", "REX_DIAG_CORR", "REX_DEBUG_SOLVER", "REX_DIAG_NOGENERAL", "REX_FAST_SINCOS",
+               "REX_LIBM_SINCOS")
+    files = [p for p in glob.glob(os.path.join(_CSRC, "*")) if os.path.isfile(p)]
+    assert os.path.join(_CSRC, "probes.hpp") in files and _SRC in files
+    for p in files:
+        text = open(p, errors="ignore").read()
+        if os.path.basename(p) != "probes.hpp":
+            found = [s for s in probe_switches if re.search(r"\b%s\b" % s, text)]
+            assert not found, "%s mentions %s" % (os.path.basename(p), found)
+        found = [s for s in deleted if re.search(r"\b%s\b" % s, text)]
+        assert not found, "%s mentions %s" % (os.path.basename(p), found)
+    probes = open(os.path.join(_CSRC, "probes.hpp")).read()
+    assert all(re.search(r"\b%s\b" % s, probes) for s in probe_switches)
 
 
 def test_rex_create_has_one_cleanup_path():

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "host_harness", "_build_humanoid_host.so")
 SRC = os.path.join(HERE, "host_harness", "humanoid_host.cpp")
 DEPS = [SRC] + [os.path.join(os.path.dirname(HERE), "random-envs_amd", "csrc", f) for f in
-                ("humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp")]
+                ("humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp", "probes.hpp")]
 
 
 @pytest.fixture(scope="module")

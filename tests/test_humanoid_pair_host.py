@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "host_harness", "_build_humanoid_pair_host.so")
 SRC = os.path.join(HERE, "host_harness", "humanoid_pair_host.cpp")
 DEPS = [SRC] + [os.path.join(os.path.dirname(HERE), "random-envs_amd", "csrc", f) for f in
-                ("humanoid_pair.hpp", "humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp")]
+                ("humanoid_pair.hpp", "humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp", "probes.hpp")]
 UB = ctypes.POINTER(ctypes.c_ubyte); I = ctypes.POINTER(ctypes.c_int)
 
 
