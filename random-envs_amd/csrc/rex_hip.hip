@@ -3,10 +3,12 @@
 // The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
 // math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp, the post-passes vecnorm.hpp and rollout.hpp.  Profiling probes
-// live in probes.hpp and are empty in this build.
+// live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
+// (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
+// goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.
 //
 // Execution model: state is SoA in HBM (qpos[nq][B], qvel[nv][B], xi[dim][B], ...), a workgroup is ONE wavefront of up to 64 lanes, and
-// the launch shape follows the batch (rex_create; "Launch shape by batch" below).  While the GPU has a SIMD for every wave an environment
+// the launch shape follows the batch (rex_create; choose_launch_shape in launch_shape.hpp).  While the GPU has a SIMD for every wave an environment
 // is split over TWO LANES (lanes 2 e and 2 e + 1 of a wave hold env e: planar chains up to 32 envs x SIMDs, the humanoid at every size);
 // past that the planar chains run one env per lane in full waves.  Either way lane accesses to a row are contiguous.  The planar per-env
 // solve (composite-inertia M, L^T D L, pyramidal contact rows, Newton) lives in VGPRs; hopper / half-cheetah model constants arrive as
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "../../include/rex.h"
+#include "launch_shape.hpp"
 #include "vecnorm.hpp"
 #include "rollout.hpp"
 #include "dev_state.hpp"
@@ -36,6 +39,8 @@
 #include "humanoid_kernels.hpp"
 
 using namespace rex;
+
+static_assert(PLAN_RS_RESAMPLE == RS_RESAMPLE && PLAN_RS_DERIVE == RS_DERIVE && PLAN_RS_REFRESH == RS_REFRESH, "reset_plan speaks the kernels' RS_* bits");
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -72,6 +77,7 @@ static const char* stray_knob() {   // a knob set without REX_ALLOW_TUNING=1, or
   return nullptr;
 }
 static const char* knob(const char* name) { return tuning_allowed() ? getenv(name) : nullptr; }
+static Knob knob_value(const char* name) { const char* e = knob(name); Knob k; if (e) { k.set = 1; k.value = atoi(e); } return k; }
 
 __global__ void fill_rows_kernel(float* dst, const float* vals, int nrows, long long B) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,13 +107,7 @@ struct rex_env {
   int full_dim = 0;                 // rows of the full xi block (dims.task_dim = rows exposed as the task)
   float* d_scratch = nullptr;   // MAX_XI floats
   float* d_chol = nullptr;      // MAX_XI*MAX_XI floats (fullgaussian Cholesky factor)
-  int lanes = 32;               // lanes per workgroup of the one-lane-per-env launches, fixed at create time (lanes_for)
-  int pair_lanes = 64;          // lanes per workgroup of the two-lanes-per-env planar step (pair_lanes_for): narrower waves while they all still get a SIMD
-  int pair = 1;                 // planar chains: two lanes per env up to 32 envs x SIMDs, one lane per env past that (REX_PAIR overrides)
-  int hum_pair = 1;             // humanoid step: two lanes per env (humanoid_pair_step_kernel; REX_HUM_PAIR=0: one env per lane)
-  int rolled = 0;               // hopper, one lane per env: the 256-register step kernel (rolled general solver, two waves per SIMD); REX_ROLLED overrides
-  int hum_fused_reset = 1;      // humanoid pair step: finished envs restart inside the step launch (REX_HUM_FUSED_RESET=0: the masked reset launch)
-  int fused_derive = 1;         // walker2d: the auto-reset under DR re-derives the lane's geometry inside the step kernel (REX_FUSED_DERIVE=0: reset + derive launches)
+  LaunchShape shape;            // lanes, blocks and kernel variants of every launch (launch_shape.hpp: choose_launch_shape at create time, rex_set_launch_shape)
   // timing: event pool created by rex_enable_timing, used as a ring by rex_step (no allocation in the step path)
   int timing = 0;
   std::vector<hipEvent_t> ev0, ev1;
@@ -144,18 +144,13 @@ static int fill_dims(int kind, int variant, rex_dims* d) {
                           d->dt = 0.015f; d->act_low = -0.4f; d->act_high = 0.4f; rc = 0; break;   // humanoid.xml:6,9; random_humanoid.py:41
     default: return -1;
   }
-  if (rc == 0 && variant) {
-    if (variant != 1 || kind == REX_CARTPOLE) return -1;
+  if (rc == 0 && variant) {   // Unmodeled ids: a prefix of xi is frozen and leaves the task vector
+    if (variant != 1 || kind == REX_CARTPOLE) return -1;   // (random_hopper_unmodeled.py:28-30, random_half_cheetah_unmodeled.py:33-36, random_walker2d_unmodeled.py:38-41)
     d->task_dim = kind == REX_HOPPER ? 3 : (kind == REX_HALFCHEETAH ? 5 : (kind == REX_WALKER2D ? 9 : 23));
   }
   return rc;
 }
-// Unmodeled ids: a prefix of xi is frozen and leaves the task vector
-// (random_hopper_unmodeled.py:28-30, random_half_cheetah_unmodeled.py:33-36, random_walker2d_unmodeled.py:38-41)
-static int variant_task_dim(int kind, int variant, int full) {
-  if (!variant) return full;
-  switch (kind) { case REX_HOPPER: return 3; case REX_HALFCHEETAH: return 5; case REX_WALKER2D: return 9; case REX_HUMANOID: return 23; default: return -1; }
-}
+// task row k of an id = row map[k] of the kernels' full xi block
 static void variant_map(int kind, int variant, int full, int* map) {
   if (!variant) { for (int k = 0; k < full; k++) map[k] = k; return; }
   switch (kind) {
@@ -188,66 +183,70 @@ static void sp_to_float(const SolParams<double>& a, SolParams<float>& b) {
 }
 
 template <class S>
-static void host_derive(rex_env* h, PlanarGeom<float, S>& out, const double* size_override = nullptr) {
-  PlanarGeom<double, S> G; SolParams<double> sp; double nominal[S::NB]; double size[8];
-  for (int k = 0; k < S::NSIZE; k++) size[k] = size_override ? size_override[k] : S::default_size[k];
+static void host_derive(rex_env* h, PlanarGeom<float, S>& out, const double* size) {
+  PlanarGeom<double, S> G; SolParams<double> sp; double nominal[S::NB];
   derive_model<double, S>(size, G, nominal, sp);
   to_float_geom<double, S>(G, out); sp_to_float(sp, h->sp);
   for (int b = 0; b < S::NB; b++) h->nominal_xi[b] = (float)nominal[b];
 }
 
-// Launch shape by batch (rex_create; measured on MI355X, DESIGN.md section 6.1 "launch shape by batch").  The step kernels are latency-bound
-// (one wave per SIMD, ~9 cycles per dependent VALU instruction against a 2-cycle issue), so as long as the GPU has a SIMD for every wave what
-// matters is the time of ONE wave, and work is spread thin: two lanes per env (`pair`, 32 envs per wave) up to 32 envs x SIMDs (MI355X: 32 768 envs),
-// 32-lane blocks for the one-lane-per-env kernels.  Past that a SIMD has several waves to run one after the other and what matters is the work
-// per env: one lane per env in full 64-lane waves (the pair split costs 1.5-1.9x the instructions per env: cheetah 65 536 envs 309 -> 528 M
-// env-steps/s, hopper 419 -> 646 M, walker 157 -> 215 M), and for the hopper past 64 envs x SIMDs the 256-register kernel whose waves share a
-// SIMD two at a time (`rolled`: 2^20 envs 866 -> 1 422 M).  The humanoid stays on two lanes per env at every size (65 536 envs: 20.5 M against 13.4 M).
 static int simds_of(int device_id) {
   int cus = 256;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || cus <= 0) cus = 256;
   return 4 * cus;
 }
-static int lanes_for(long long B, int simds) {
-  const char* e = knob("REX_LANES");
-  if (e && atoi(e) > 0) return atoi(e);
-  return B > 32ll * simds ? 64 : 32;
+// grid and block of the one-lane-per-env launches; dynamic LDS of the humanoid kernels: one dual-PGS column (hum::DUAL_WORDS floats) per lane
+// (all three read the handle's one LaunchShape: grid, block and dynamic-LDS size always agree)
+static dim3 grid_for(const rex_env* h) { return dim3(h->shape.grid(h->B)); }
+static dim3 lanes_of(const rex_env* h) { return dim3(h->shape.block()); }
+static size_t hum_lds_bytes(const rex_env* h) { return sizeof(float) * hum::DUAL_WORDS * (size_t)h->shape.lanes; }
+
+// ------------------------------------------------------------------------------------------
+// the one dispatch over the env kind
+// ------------------------------------------------------------------------------------------
+// with_kind(h, f) calls f with a tag for the handle's kind: the three planar chains share PlanarTag<Spec> (the Spec type and the handle's
+// model constants of that Spec), the cart-pole and the humanoid have tags of their own.  Callers are generic lambdas that branch with
+// `if constexpr` on the tag's family, so a kind's kernels are instantiated only where with_kind hands out its tag -- which it does for the
+// kinds this build compiles (-DREX_ONLY_KIND tuning builds: dev_state.hpp) and for no other; nothing is called for a kind that is not compiled.
+struct CartpoleTag { static constexpr bool cartpole = true, planar = false, humanoid = false; };
+struct HumanoidTag { static constexpr bool cartpole = false, planar = false, humanoid = true; };
+template <class S> struct PlanarTag { static constexpr bool cartpole = false, planar = true, humanoid = false; using Spec = S; PlanarGeom<float, S>& geom; };
+template <class F> static void with_kind(rex_env* h, F&& f) {
+  switch (h->kind) {
+    case REX_CARTPOLE:    if constexpr (REX_EN_CARTPOLE) f(CartpoleTag{}); break;
+    case REX_HOPPER:      if constexpr (REX_EN_HOPPER) f(PlanarTag<HopperSpec>{h->g_hopper}); break;
+    case REX_HALFCHEETAH: if constexpr (REX_EN_HALFCHEETAH) f(PlanarTag<HalfCheetahSpec>{h->g_cheetah}); break;
+    case REX_WALKER2D:    if constexpr (REX_EN_WALKER2D) f(PlanarTag<Walker2dSpec>{h->g_walker}); break;
+    case REX_HUMANOID:    if constexpr (REX_EN_HUMANOID) f(HumanoidTag{}); break;
+  }
 }
-// Two lanes per env: a step launch costs ONE wave's latency while every wave has a SIMD to itself, and a wave pays for the slowest of its envs in
-// every Newton pass -- so a walker2d / half-cheetah batch that leaves SIMDs idle is spread over them in narrower waves (16 384 envs: 32-lane
-// blocks = 16 envs per wave, 8 192: 16 lanes): fewer envs to wait for per pass (walker2d: 26.5 -> 21.0 passes per wave-step at 16 lanes).  Two
-// limits, both measured (profiles/HISTORY.md, round 4; profiles/waveplace_probe.py):
-//  - a CU with fewer than 64 ACTIVE lanes on it runs the same instruction stream slower (walker2d, cycles per Newton pass: 12.5 k with one 64-lane
-//    wave on the CU, 13.1 k with four 16-lane waves, 14.2 k with one 32-lane wave, 18.8 k with two 16-lane waves -- same clock, same pass
-//    counts, one wave per SIMD in every case), so below 8 envs per SIMD (8 192 envs) the blocks stay 64 lanes wide;
-//  - the hopper's waves gain nothing from being narrow (its slowest wave is set by the feet-only passes every env runs): always 64 lanes.
-static int pair_lanes_for(int kind, long long B, int simds) {
-  const char* e = knob("REX_LANES");
-  if (e && atoi(e) > 0) return atoi(e);
-  if (kind == REX_HOPPER || B < 8ll * simds) return 64;
-  int L = 64;
-  while (L > 16 && (4 * B + L - 1) / L <= (long long)simds) L /= 2;   // halve while the halved blocks still number <= SIMDs
-  return L;
-}
-// dynamic LDS of the humanoid kernels: one dual-PGS column (hum::DUAL_WORDS floats) per lane
-// (read once in rex_create and cached in the handle: grid, block and dynamic-LDS size always agree)
-static size_t hum_lds_bytes(const rex_env* h) { return sizeof(float) * hum::DUAL_WORDS * (size_t)h->lanes; }
-static unsigned grid_for(const rex_env* h) { return (unsigned)((h->B + h->lanes - 1) / h->lanes); }
-static unsigned lanes_of(const rex_env* h) { return (unsigned)h->lanes; }
 
 constexpr int DERIVE_PENDING_BIT = 4;   // in DevState::done: reset under DR, geometry not yet re-derived (walker2d auto-reset)
-static int launch_walker_derive(rex_env* h, const unsigned char* mask, int bit, hipStream_t st, int task_changed) {
-#if REX_EN_WALKER2D
+// walker2d: per-env geometry rows of `dev` from its xi lengths (the handle's own state, or rex_replay's view of the caller's)
+static int launch_walker_derive(rex_env* h, const DevState& dev, const unsigned char* mask, int bit, hipStream_t st, int task_changed) {
+#if REX_EN_WALKER2D   // (the kernel exists in builds with the walker2d only)
   const bool auto_mask = mask == h->dev.done;   // the auto-reset path: the reset launch replaced the done bit by the pending bit
-  hipLaunchKernelGGL(walker_derive_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), 0, st, h->dev, mask, auto_mask ? DERIVE_PENDING_BIT : bit,
+  hipLaunchKernelGGL(walker_derive_kernel, grid_for(h), lanes_of(h), 0, st, dev, mask, auto_mask ? DERIVE_PENDING_BIT : bit,
                      (h->variant && task_changed) ? 1 : 0, auto_mask ? 1 : 0);
   HIP_TRY(hipGetLastError());
 #endif
   return REX_OK;
 }
 
-// the humanoid's compiled model: built once per process (magic static: thread-safe), shared by every handle
+// dst[k][:] = host_vals[k] for nrows rows of a [rows][B] block, through the handle's d_scratch (the synchronise keeps a row fill still in
+// flight from reading the next call's values)
+static int launch_fill_rows(rex_env* h, float* dst, const float* host_vals, int nrows) {
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->d_scratch, host_vals, sizeof(float) * nrows, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, 0, dst, h->d_scratch, nrows, h->B);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+// Everything that names a humanoid kernel or hum:: model type.  The launchers take the tag so that a generic lambda's call to them is
+// resolved only where with_kind hands out a HumanoidTag: a build without the humanoid has none of this and never asks for it.
 #if REX_EN_HUMANOID
+// the humanoid's compiled model: built once per process (magic static: thread-safe), shared by every handle
 struct HumModels { hum::Model<double> md; hum::Model<float> mf; const char* err = nullptr; };
 static const HumModels& hum_models() {
   static const HumModels* m = [] {
@@ -260,14 +259,66 @@ static const HumModels& hum_models() {
   }();
   return *m;
 }
+// create_body's share: the model in constant memory, the kernels' LDS limit, the nominal task, qpos0 and the xipos rows
+static int humanoid_create(HumanoidTag, rex_env* h, float* q0, float* noise_var) {
+  const HumModels& hm = hum_models();
+  if (hm.err) return set_err(REX_ERR_ARG, "%s", hm.err);
+  const hum::Model<double>& md = hm.md;
+  { hum::Model<float> up = hm.mf;
+#if defined(REX_TUNING)   // timing experiments only (changes the physics): a cap on the PGS sweeps
+    if (knob("REX_HUM_ITERS")) up.iterations = atoi(knob("REX_HUM_ITERS"));
+#endif
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_hum), &up, sizeof up)); }
+  {   // 64-lane blocks need more than the default 64 KB of dynamic LDS
+    const int lds = (int)(sizeof(float) * hum::DUAL_WORDS * 64);
+    HIP_TRY(hipFuncSetAttribute((const void*)humanoid_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute((const void*)humanoid_reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute((const void*)humanoid_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  }
+  for (int b = 0; b < 13; b++) h->nominal_xi[b] = (float)md.body_mass0[1 + b];          // random_humanoid.py:46
+  for (int k = 0; k < 17; k++) h->nominal_xi[13 + k] = (float)md.dof_damping0[6 + k];   // :47
+  if (h->variant) {   // random_humanoid_unmodeled.py:40-50: masses 1..4 and dampings 6..8 frozen at 0.8x
+    for (int b = 0; b < 4; b++) h->nominal_xi[b] *= 0.8f;
+    for (int k = 0; k < 3; k++) h->nominal_xi[13 + k] *= 0.8f;
+  }
+  HIP_TRY(hipMalloc(&h->dev.aux, sizeof(float) * hum::NBODY * (size_t)h->B));
+  HIP_TRY(hipMemset(h->dev.aux, 0, sizeof(float) * hum::NBODY * (size_t)h->B));
+  q0[2] = 1.4f; q0[3] = 1.0f;                                                             // humanoid.xml:30,32
+  *noise_var = 1e-3f;                                                                     // random_humanoid.py:39
+  return REX_OK;
+}
+static void launch_humanoid_reset(HumanoidTag, rex_env* h, int resample, int reset_state, const unsigned char* mask, int bit, float* obs, hipStream_t st) {
+  hipLaunchKernelGGL(humanoid_reset_kernel, grid_for(h), lanes_of(h), hum_lds_bytes(h), st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs);
+}
+// sim.forward(): data.xipos of `dev`'s state into dev.aux, and the observation into obs_out when given
+static int launch_humanoid_forward(HumanoidTag, rex_env* h, const DevState& dev, float* obs_out, hipStream_t st) {
+  hipLaunchKernelGGL(humanoid_forward_kernel, grid_for(h), lanes_of(h), hum_lds_bytes(h), st, dev, obs_out);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+static void launch_humanoid_step(HumanoidTag, rex_env* h, const DevState& dev, const StepFlags& flags, const float* action, float* obs_out, float* reward_out,
+                                 uint8_t* done_out, uint8_t* truncated_out, float* terminal_obs_out, hipStream_t st, int fused = 0, int resample = 0) {
+  if (h->shape.hum_pair) {   // 2 B lanes in 64-lane blocks: 32 envs per wave, one LDS column per env
+    const unsigned blocks = (unsigned)((2 * h->B + 63) / 64);
+    hipLaunchKernelGGL(humanoid_pair_step_kernel, dim3(blocks), dim3(64), sizeof(float) * hum::pr::PAIR_WORDS * 32, st, dev, flags, action, obs_out,
+                       reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
+  } else {
+    hipLaunchKernelGGL(humanoid_step_kernel, grid_for(h), lanes_of(h), hum_lds_bytes(h), st, dev, flags, action, obs_out, reward_out,
+                       done_out, truncated_out, terminal_obs_out);
+  }
+}
 #endif
 
 // everything of rex_create that can fail after the handle exists: on any error the caller destroys the handle, which frees
 // whatever was allocated up to that point (every device pointer of a fresh rex_env is null)
 static int create_body(rex_env* h, int env_kind, int variant, int64_t batch, int device_id, const rex_dims& dims, const rex_dims& full) {
-  const int simds = simds_of(device_id);
-  h->lanes = lanes_for(batch, simds);
-  if (h->lanes < 8 || h->lanes > 64 || (h->lanes & (h->lanes - 1))) return set_err(REX_ERR_ARG, "REX_LANES must be 8, 16, 32 or 64 (got %d)", h->lanes);
+  {   // the launch shape: the batch, the GPU's SIMD count and the shape knobs (launch_shape.hpp); rex_set_launch_shape overrides it per handle
+    ShapeKnobs k;
+    k.lanes = knob_value("REX_LANES"); k.pair = knob_value("REX_PAIR"); k.rolled = knob_value("REX_ROLLED"); k.hum_pair = knob_value("REX_HUM_PAIR");
+    k.hum_fused_reset = knob_value("REX_HUM_FUSED_RESET"); k.fused_derive = knob_value("REX_FUSED_DERIVE"); k.fast = knob_value("REX_FAST");
+    const char* why = nullptr;
+    if (int rc = choose_launch_shape(env_kind, batch, simds_of(device_id), k, &h->shape, &why)) return set_err(rc, "%s", why);
+  }
   h->dims = dims;
   h->flags.endless = 0; h->flags.noisy = 0; h->flags.time_limit = 1; h->flags.max_steps = dims.max_episode_steps;
   h->flags.noise_std = 0.0f; h->flags.info = nullptr; h->flags.readonly = 0;
@@ -295,52 +346,34 @@ static int create_body(rex_env* h, int env_kind, int variant, int64_t batch, int
   HIP_TRY(hipMemset(d.done, 0, B));
   HIP_TRY(hipMemset(d.counters, 0, sizeof(unsigned long long) * 4));
   d.geom = nullptr; d.aux = nullptr;
-  float noise_var = 0;
-  switch (env_kind) {
-    case REX_CARTPOLE: { const float t0[4] = {9.8f, 1.0f, 0.1f, 0.5f}; memcpy(h->nominal_xi, t0, sizeof t0); break; }   // random_cartpole.py:74-78
-    case REX_HOPPER: host_derive<HopperSpec>(h, h->g_hopper); noise_var = HopperSpec::DEFAULT_NOISE_VAR;
-                     if (variant) h->nominal_xi[0] *= 0.8f;                                                               // random_hopper_unmodeled.py:24-26
-                     break;
-    case REX_HALFCHEETAH: host_derive<HalfCheetahSpec>(h, h->g_cheetah); h->nominal_xi[7] = 0.4f;                        // random_half_cheetah.py:37
-                          if (variant) for (int b = 0; b < 3; b++) h->nominal_xi[b] *= 0.8f;                             // random_half_cheetah_unmodeled.py:28-31
-                          noise_var = HalfCheetahSpec::DEFAULT_NOISE_VAR; break;
-    case REX_WALKER2D: {
-      double wsize[4]; for (int k = 0; k < 4; k++) wsize[k] = Walker2dSpec::default_size[k];
-      if (variant) wsize[0] *= 0.8;                                                                                      // random_walker2d_unmodeled.py:25-27
-      host_derive<Walker2dSpec>(h, h->g_walker, wsize);
-      if (variant) for (int b = 0; b < 3; b++) h->nominal_xi[b] *= 0.8f;                                                 // :33-36 (until the first set_task, Q6)
-      for (int k = 0; k < 4; k++) h->nominal_xi[7 + k] = (float)wsize[k];                                                // random_walker2d.py:21
-      h->nominal_xi[11] = 0.9f; h->nominal_xi[12] = 1.9f;                                                                // random_walker2d.py:37
-      HIP_TRY(hipMalloc(&d.geom, sizeof(float) * kWalkerCompact * B));
-      noise_var = Walker2dSpec::DEFAULT_NOISE_VAR; break; }
-#if REX_EN_HUMANOID
-    case REX_HUMANOID: {
-      const HumModels& hm = hum_models();
-      if (hm.err) return set_err(REX_ERR_ARG, "%s", hm.err);
-      const hum::Model<double>& md = hm.md;
-      { hum::Model<float> up = hm.mf;
-#if defined(REX_TUNING)   // timing experiments only (changes the physics): a cap on the PGS sweeps
-        if (knob("REX_HUM_ITERS")) up.iterations = atoi(knob("REX_HUM_ITERS"));
-#endif
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_hum), &up, sizeof up)); }
-      {   // 64-lane blocks need more than the default 64 KB of dynamic LDS
-        const int lds = (int)(sizeof(float) * hum::DUAL_WORDS * 64);
-        HIP_TRY(hipFuncSetAttribute((const void*)humanoid_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)humanoid_reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)humanoid_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  // per kind: the model constants, the nominal task (nominal_xi), the rows of qpos0 that are not 0, the default observation noise
+  float noise_var = 0, q0[MAX_XI] = {0};
+  bool has_q0 = false;
+  int rc = REX_OK;
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::cartpole) {
+      const float t0[4] = {9.8f, 1.0f, 0.1f, 0.5f}; memcpy(h->nominal_xi, t0, sizeof t0);                                  // random_cartpole.py:74-78
+    } else if constexpr (Tag::planar) {
+      using S = typename Tag::Spec;
+      double size[8]; for (int k = 0; k < S::NSIZE; k++) size[k] = S::default_size[k];
+      if (S::KIND == REX_WALKER2D && variant) size[0] *= 0.8;                                                              // random_walker2d_unmodeled.py:25-27
+      host_derive<S>(h, tag.geom, size); noise_var = S::DEFAULT_NOISE_VAR;
+      // Unmodeled ids freeze the leading masses at 0.8x: random_hopper_unmodeled.py:24-26, random_half_cheetah_unmodeled.py:28-31,
+      // random_walker2d_unmodeled.py:33-36 (until the first set_task, Q6)
+      if (variant) for (int b = 0; b < (S::KIND == REX_HOPPER ? 1 : 3); b++) h->nominal_xi[b] *= 0.8f;
+      if (S::KIND == REX_HALFCHEETAH) h->nominal_xi[7] = 0.4f;                                                             // random_half_cheetah.py:37
+      else { q0[1] = 1.25f; has_q0 = true; }                                                                               // the hopper and the walker2d start standing
+      if (S::KIND == REX_WALKER2D) {
+        for (int k = 0; k < 4; k++) h->nominal_xi[7 + k] = (float)size[k];                                                 // random_walker2d.py:21
+        h->nominal_xi[11] = 0.9f; h->nominal_xi[12] = 1.9f;                                                                // random_walker2d.py:37
       }
-      for (int b = 0; b < 13; b++) h->nominal_xi[b] = (float)md.body_mass0[1 + b];          // random_humanoid.py:46
-      for (int k = 0; k < 17; k++) h->nominal_xi[13 + k] = (float)md.dof_damping0[6 + k];   // :47
-      if (variant) {   // random_humanoid_unmodeled.py:40-50: masses 1..4 and dampings 6..8 frozen at 0.8x
-        for (int b = 0; b < 4; b++) h->nominal_xi[b] *= 0.8f;
-        for (int k = 0; k < 3; k++) h->nominal_xi[13 + k] *= 0.8f;
-      }
-      HIP_TRY(hipMalloc(&d.aux, sizeof(float) * hum::NBODY * B));
-      HIP_TRY(hipMemset(d.aux, 0, sizeof(float) * hum::NBODY * B));
-      noise_var = 1e-3f;                                                                      // :39
-      break; }
-#endif
-  }
+    } else {
+      rc = humanoid_create(tag, h, q0, &noise_var); has_q0 = true;
+    }
+  });
+  if (rc) return rc;
+  if (env_kind == REX_WALKER2D) HIP_TRY(hipMalloc(&d.geom, sizeof(float) * kWalkerCompact * B));
   h->flags.noise_std = sqrtf(noise_var);
 #if defined(REX_TUNING)   // timing diagnostics only (changes the physics): no floor contacts ever
   if (knob("REX_DIAG_NOCONTACT")) h->sp.con_margin = -1e9f;
@@ -351,45 +384,12 @@ static int create_body(rex_env* h, int env_kind, int variant, int64_t batch, int
   if (knob("REX_LS_FREE")) h->sp.ls_free = atoi(knob("REX_LS_FREE"));
   if (knob("REX_CORR")) h->sp.corr = atoi(knob("REX_CORR"));
   if (knob("REX_FAST")) h->sp.fast = atoi(knob("REX_FAST"));
-  // launch shape by batch (lanes_for above has the measurements); rex_set_launch_shape overrides it per handle
-  h->pair = batch <= 32ll * simds ? 1 : 0;
-  h->pair_lanes = pair_lanes_for(env_kind, batch, simds);
-  if (h->pair_lanes < 8 || h->pair_lanes > 64 || (h->pair_lanes & (h->pair_lanes - 1))) return set_err(REX_ERR_ARG, "REX_LANES must be 8, 16, 32 or 64 (got %d)", h->pair_lanes);
-  h->rolled = (env_kind == REX_HOPPER && batch > 64ll * simds) ? 1 : 0;
-  if (knob("REX_PAIR")) h->pair = atoi(knob("REX_PAIR")) ? 1 : 0;
-  if (knob("REX_ROLLED")) h->rolled = (env_kind == REX_HOPPER && atoi(knob("REX_ROLLED"))) ? 1 : 0;
-  if (knob("REX_HUM_PAIR")) h->hum_pair = atoi(knob("REX_HUM_PAIR")) ? 1 : 0;
-  if (knob("REX_HUM_FUSED_RESET")) h->hum_fused_reset = atoi(knob("REX_HUM_FUSED_RESET")) ? 1 : 0;
-  // walker2d: derive fused into the step kernel (inlined in the pair kernel, a call in the one-lane one) while the two small launches behind a
-  // step are a visible share of it (32 768 envs: + 10 % env-steps/s, 65 536: + 9 %, 131 072: + 4.5 %, 2^20: - 0.5 %)
-  h->fused_derive = batch < 524288 ? 1 : 0;
-  if (knob("REX_FUSED_DERIVE")) h->fused_derive = atoi(knob("REX_FUSED_DERIVE")) ? 1 : 0;
-  if (!h->sp.fast && !knob("REX_PAIR")) h->pair = 0;   // REX_FAST=0 is the strict-lane-independence mode: one lane per env unless REX_PAIR asks for the pair kernel
-                                                        // (whose general path is the list solver: REX_FAST=0 REX_PAIR=1 runs it on every lane)
-  if (h->pair) h->rolled = 0;     // the two-waves-per-SIMD kernel is a one-lane-per-env one
-  // xi <- nominal task, state <- qpos0
-  HIP_TRY(hipMemcpy(h->d_scratch, h->nominal_xi, sizeof(float) * full.task_dim, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, 0, d.xi, h->d_scratch, full.task_dim, (long long)B);
-  HIP_TRY(hipGetLastError());
-  if (env_kind == REX_WALKER2D) { int rc = launch_walker_derive(h, nullptr, 0, 0, 0); if (rc) return rc; }
-#if REX_EN_HUMANOID
-  if (env_kind == REX_HUMANOID) {
-    float q0[MAX_XI] = {0}; q0[2] = 1.4f; q0[3] = 1.0f;                                       // humanoid.xml:30,32
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h->d_scratch, q0, sizeof(float) * dims.nq, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, 0, d.qpos, h->d_scratch, dims.nq, (long long)B);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(humanoid_forward_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), hum_lds_bytes(h), 0, h->dev, (float*)nullptr);
-    HIP_TRY(hipGetLastError());
-  }
-#endif
-  if (env_kind == REX_HOPPER || env_kind == REX_WALKER2D) {
-    float q0[MAX_XI] = {0}; q0[1] = 1.25f;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h->d_scratch, q0, sizeof(float) * dims.nq, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, 0, d.qpos, h->d_scratch, dims.nq, (long long)B);
-    HIP_TRY(hipGetLastError());
-  }
+  // xi <- nominal task, state <- qpos0 (the rows of qpos0 that are 0 were cleared above)
+  if ((rc = launch_fill_rows(h, d.xi, h->nominal_xi, full.task_dim))) return rc;
+  if (env_kind == REX_WALKER2D && (rc = launch_walker_derive(h, h->dev, nullptr, 0, 0, 0))) return rc;
+  if (has_q0 && (rc = launch_fill_rows(h, d.qpos, q0, dims.nq))) return rc;
+  with_kind(h, [&](auto tag) { if constexpr (decltype(tag)::humanoid) rc = launch_humanoid_forward(tag, h, h->dev, nullptr, 0); });
+  if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
   return REX_OK;
 }
@@ -486,37 +486,30 @@ extern "C" int rex_set_autoreset(rex_t* h, int autoreset, int time_limit) {
 extern "C" int rex_seed(rex_t* h, uint64_t seed) { if (!h) return set_err(REX_ERR_ARG, "null handle"); h->seed = seed; h->dev.seed = seed; return REX_OK; }
 
 static int do_reset(rex_t* h, const unsigned char* mask, int bit, int resample, int reset_state, float* obs, hipStream_t st) {
-  const dim3 g(grid_for(h)), b(lanes_of(h));
+  const dim3 g = grid_for(h), b = lanes_of(h);
   if (resample && h->dr.type == REX_DR_NONE) return set_err(REX_ERR_STATE,
       "sampling value of random env needs to be set before using sample_task() or set_random_task()");   // random_env.py:201
-  switch (h->kind) {
-#if REX_EN_CARTPOLE
-    case REX_CARTPOLE: hipLaunchKernelGGL(cartpole_reset_kernel, g, b, 0, st, h->dev, h->dr, resample, reset_state, mask, bit, obs); break;
-#endif
-#if REX_EN_HOPPER
-    case REX_HOPPER: hipLaunchKernelGGL(planar_reset_kernel<HopperSpec>, g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs, 0); break;
-#endif
-#if REX_EN_HALFCHEETAH
-    case REX_HALFCHEETAH: hipLaunchKernelGGL(planar_reset_kernel<HalfCheetahSpec>, g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs, 0); break;
-#endif
-#if REX_EN_WALKER2D
-    case REX_WALKER2D: hipLaunchKernelGGL(planar_reset_kernel<Walker2dSpec>, g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs,
-                                          (resample && mask == h->dev.done) ? DERIVE_PENDING_BIT : 0); break;
-#endif
-#if REX_EN_HUMANOID
-    case REX_HUMANOID: hipLaunchKernelGGL(humanoid_reset_kernel, g, b, hum_lds_bytes(h), st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs); break;
-#endif
-  }
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::cartpole) {
+      hipLaunchKernelGGL(cartpole_reset_kernel, g, b, 0, st, h->dev, h->dr, resample, reset_state, mask, bit, obs);
+    } else if constexpr (Tag::planar) {   // walker2d auto-reset under DR: the done bit becomes the pending bit, the derive launch below clears it
+      using S = typename Tag::Spec;
+      hipLaunchKernelGGL(planar_reset_kernel<S>, g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs,
+                         (S::KIND == REX_WALKER2D && resample && mask == h->dev.done) ? DERIVE_PENDING_BIT : 0);
+    } else {
+      launch_humanoid_reset(tag, h, resample, reset_state, mask, bit, obs, st);
+    }
+  });
   HIP_TRY(hipGetLastError());
-  if (h->kind == REX_WALKER2D && resample) return launch_walker_derive(h, mask, bit, st, 1);
+  if (h->kind == REX_WALKER2D && resample) return launch_walker_derive(h, h->dev, mask, bit, st, 1);
   return REX_OK;
 }
 
 extern "C" int rex_reset(rex_t* h, const uint8_t* mask, float* obs_out, void* stream) {
   REX_ENTER(h, "rex_reset");
-  // CartPole.reset() never resamples (random_cartpole.py:226-229); the MuJoCo envs do when dr_training
-  int resample = (h->dr_training && h->kind != REX_CARTPOLE) ? 1 : 0;
-  return do_reset(h, mask, 1, resample, 1, obs_out, (hipStream_t)stream);
+  const ResetPlan plan = reset_plan(h->kind, h->variant, h->autoreset, h->dr_training, h->dr.type, h->shape);
+  return do_reset(h, mask, 1, plan.resample, 1, obs_out, (hipStream_t)stream);
 }
 extern "C" int rex_set_random_task(rex_t* h, const uint8_t* mask, void* stream) {
   REX_ENTER(h, "rex_set_random_task");
@@ -527,81 +520,60 @@ template <class S>
 static void launch_planar_step(rex_env* h, const DevState& dev, const StepFlags& flags, const PlanarGeom<float, S>& geom, const float* action,
                                float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* truncated_out, float* terminal_obs_out,
                                int fused, int resample, hipStream_t st) {
-  if (h->pair) {   // 2 B lanes in blocks of pair_lanes: 32 envs per wave, fewer for a walker2d / half-cheetah batch of 8 192 .. 16 384 (pair_lanes_for)
-    const unsigned L = (unsigned)h->pair_lanes, blocks = (unsigned)((2 * h->B + L - 1) / L);
+  if (h->shape.pair) {   // 2 B lanes in blocks of pair_lanes: 32 envs per wave, fewer for a walker2d / half-cheetah batch of 8 192 .. 16 384 (choose_launch_shape)
+    const unsigned L = (unsigned)h->shape.pair_lanes, blocks = (unsigned)((2 * h->B + L - 1) / L);
     hipLaunchKernelGGL((planar_step_kernel<S, true>), dim3(blocks), dim3(L), 0, st, dev, flags, geom, h->sp, action, obs_out, reward_out,
                        done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
   } else {
     if constexpr (S::KIND == 1) {
-      if (h->rolled) {   // two waves per SIMD (rex_create: more full waves than SIMDs)
-        hipLaunchKernelGGL((planar_step_kernel<S, false, true>), dim3(grid_for(h)), dim3(lanes_of(h)), 0, st, dev, flags, geom, h->sp, action, obs_out,
+      if (h->shape.rolled) {   // two waves per SIMD (rex_create: more full waves than SIMDs)
+        hipLaunchKernelGGL((planar_step_kernel<S, false, true>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
                            reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
         return;
       }
     }
-    hipLaunchKernelGGL((planar_step_kernel<S, false>), dim3(grid_for(h)), dim3(lanes_of(h)), 0, st, dev, flags, geom, h->sp, action, obs_out,
+    hipLaunchKernelGGL((planar_step_kernel<S, false>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
                        reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
   }
 }
 
-#if REX_EN_HUMANOID
-static void launch_humanoid_step(rex_env* h, const DevState& dev, const StepFlags& flags, const float* action, float* obs_out, float* reward_out,
-                                 uint8_t* done_out, uint8_t* truncated_out, float* terminal_obs_out, hipStream_t st, int fused = 0, int resample = 0) {
-  if (h->hum_pair) {   // 2 B lanes in 64-lane blocks: 32 envs per wave, one LDS column per env
-    const unsigned blocks = (unsigned)((2 * h->B + 63) / 64);
-    hipLaunchKernelGGL(humanoid_pair_step_kernel, dim3(blocks), dim3(64), sizeof(float) * hum::pr::PAIR_WORDS * 32, st, dev, flags, action, obs_out,
-                       reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
-  } else {
-    hipLaunchKernelGGL(humanoid_step_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), hum_lds_bytes(h), st, dev, flags, action, obs_out, reward_out,
-                       done_out, truncated_out, terminal_obs_out);
-  }
+// The sampled event bracket of rex_step / rex_replay: every `timing`-th call is bracketed by two events of the pool rex_enable_timing
+// created (ring; no allocation here): the two event packets cost ~8 us of stream time per launch, 9 % of a hopper step, so a throughput
+// run samples (bench.py: every 8th launch).  The second record follows the last launch of the call.
+struct TimedCall { bool on; size_t slot; };
+static int launch_timing_begin(rex_env* h, hipStream_t st, TimedCall* t) {
+  t->on = h->timing > 0 && (h->launches++ % (unsigned long long)h->timing) == 0;
+  t->slot = t->on ? h->ev_n % h->ev0.size() : 0;   // (timing > 0 implies a complete pool)
+  if (t->on) HIP_TRY(hipEventRecord(h->ev0[t->slot], st));
+  return REX_OK;
 }
-#endif
+static int launch_timing_end(rex_env* h, hipStream_t st, const TimedCall& t) {
+  if (t.on) { HIP_TRY(hipEventRecord(h->ev1[t.slot], st)); h->ev_n++; }
+  return REX_OK;
+}
 
 extern "C" int rex_step(rex_t* h, const void* action, float* obs_out, float* reward_out, uint8_t* done_out,
                         uint8_t* truncated_out, float* terminal_obs_out, void* stream) {
   REX_ENTER(h, "rex_step");
   if (!action || !obs_out || !reward_out || !done_out) return set_err(REX_ERR_ARG, "rex_step: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  const dim3 g(grid_for(h)), b(lanes_of(h));
-  const int resample_on_reset = (h->dr_training && h->kind != REX_CARTPOLE) ? 1 : 0;
   // planar envs reset finished lanes inside the step kernel (walker2d under DR re-derives the lane's geometry there as well)
-  const bool walker_dr = h->kind == REX_WALKER2D && resample_on_reset && h->dr.type != REX_DR_NONE;
-  const int fused = (h->autoreset && (h->kind == REX_HOPPER || h->kind == REX_HALFCHEETAH || (h->kind == REX_WALKER2D && (!walker_dr || h->fused_derive)) ||
-                                      (h->kind == REX_HUMANOID && h->hum_pair && h->hum_fused_reset))) ? 1 : 0;
-  int rs = resample_on_reset ? RS_RESAMPLE : 0;
-  if (walker_dr && h->fused_derive) rs |= RS_DERIVE | (h->variant ? RS_REFRESH : 0);
-  // every `timing`-th launch is bracketed by two events of the pool rex_enable_timing created (ring): the two event packets
-  // cost ~8 us of stream time per launch, 9 % of a hopper step, so a throughput run samples (bench.py: every 8th launch)
-  const bool timed = h->timing > 0 && (h->launches++ % (unsigned long long)h->timing) == 0;
-  const size_t ev_slot = timed ? h->ev_n % h->ev0.size() : 0;   // (timing > 0 implies a complete pool)
-  if (timed) HIP_TRY(hipEventRecord(h->ev0[ev_slot], st));
-  switch (h->kind) {
-#if REX_EN_CARTPOLE
-    case REX_CARTPOLE:
-      hipLaunchKernelGGL(cartpole_step_kernel, g, b, 0, st, h->dev, h->flags, (const int*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out); break;
-#endif
-#if REX_EN_HOPPER
-    case REX_HOPPER:
-      launch_planar_step<HopperSpec>(h, h->dev, h->flags, h->g_hopper, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, fused, rs, st); break;
-#endif
-#if REX_EN_HALFCHEETAH
-    case REX_HALFCHEETAH:
-      launch_planar_step<HalfCheetahSpec>(h, h->dev, h->flags, h->g_cheetah, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, fused, rs, st); break;
-#endif
-#if REX_EN_WALKER2D
-    case REX_WALKER2D:
-      launch_planar_step<Walker2dSpec>(h, h->dev, h->flags, h->g_walker, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, fused, rs, st); break;
-#endif
-#if REX_EN_HUMANOID
-    case REX_HUMANOID:
-      launch_humanoid_step(h, h->dev, h->flags, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, st, fused, resample_on_reset); break;
-#endif
-  }
-  if (timed) { HIP_TRY(hipEventRecord(h->ev1[ev_slot], st)); h->ev_n++; }
+  const ResetPlan plan = reset_plan(h->kind, h->variant, h->autoreset, h->dr_training, h->dr.type, h->shape);
+  TimedCall timed;
+  if (int rc = launch_timing_begin(h, st, &timed)) return rc;
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::cartpole)
+      hipLaunchKernelGGL(cartpole_step_kernel, grid_for(h), lanes_of(h), 0, st, h->dev, h->flags, (const int*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out);
+    else if constexpr (Tag::planar)
+      launch_planar_step<typename Tag::Spec>(h, h->dev, h->flags, tag.geom, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, plan.fused, plan.rs, st);
+    else
+      launch_humanoid_step(tag, h, h->dev, h->flags, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, st, plan.fused, plan.resample);
+  });
+  if (int rc = launch_timing_end(h, st, timed)) return rc;
   HIP_TRY(hipGetLastError());
   h->step_count += h->B;
-  if (h->autoreset && !fused) return do_reset(h, h->dev.done, 2, resample_on_reset, 1, obs_out, st);
+  if (h->autoreset && !plan.fused) return do_reset(h, h->dev.done, 2, plan.resample, 1, obs_out, st);
   return REX_OK;
 }
 
@@ -661,39 +633,26 @@ extern "C" int rex_replay(rex_t* h, const float* qpos, const float* qvel, const 
     HIP_TRY(hipGetLastError());
     dev.xi = h->rp_xi;
   }
-#if REX_EN_WALKER2D
   if (h->kind == REX_WALKER2D) {             // geometry of the caller's xi lengths (what set_task's build_model does)
     dev.geom = h->rp_rows;
-    hipLaunchKernelGGL(walker_derive_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), 0, st, dev, (const unsigned char*)nullptr, 0, h->variant ? 1 : 0, 0);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_walker_derive(h, dev, nullptr, 0, st, 1)) return rc;
   }
-#endif
   StepFlags flags = h->flags; flags.readonly = 1; flags.info = nullptr;
-  const bool timed = h->timing > 0 && (h->launches++ % (unsigned long long)h->timing) == 0;   // same sampling as rex_step
-  const size_t ev_slot = timed ? h->ev_n % h->ev0.size() : 0;
-  if (timed) HIP_TRY(hipEventRecord(h->ev0[ev_slot], st));
-  switch (h->kind) {
-#if REX_EN_HOPPER
-    case REX_HOPPER: launch_planar_step<HopperSpec>(h, dev, flags, h->g_hopper, action, obs_out, reward_out, done_out, nullptr, nullptr, 0, 0, st); break;
-#endif
-#if REX_EN_HALFCHEETAH
-    case REX_HALFCHEETAH: launch_planar_step<HalfCheetahSpec>(h, dev, flags, h->g_cheetah, action, obs_out, reward_out, done_out, nullptr, nullptr, 0, 0, st); break;
-#endif
-#if REX_EN_WALKER2D
-    case REX_WALKER2D: launch_planar_step<Walker2dSpec>(h, dev, flags, h->g_walker, action, obs_out, reward_out, done_out, nullptr, nullptr, 0, 0, st); break;
-#endif
-#if REX_EN_HUMANOID
-    case REX_HUMANOID:   // set_state's sim.forward() (jinja_mujoco_env.py:154) leaves data.xipos for mass_center(): a forward launch into
-                         // replay scratch, then the step launch
-      dev.aux = h->rp_rows;
-      hipLaunchKernelGGL(humanoid_forward_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), hum_lds_bytes(h), st, dev, (float*)nullptr);
-      HIP_TRY(hipGetLastError());
-      launch_humanoid_step(h, dev, flags, action, obs_out, reward_out, done_out, nullptr, nullptr, st);
-      break;
-#endif
-    default: break;
-  }
-  if (timed) { HIP_TRY(hipEventRecord(h->ev1[ev_slot], st)); h->ev_n++; }
+  TimedCall timed;                           // same sampling as rex_step
+  if (int rc = launch_timing_begin(h, st, &timed)) return rc;
+  int rc = REX_OK;
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::planar) {
+      launch_planar_step<typename Tag::Spec>(h, dev, flags, tag.geom, action, obs_out, reward_out, done_out, nullptr, nullptr, 0, 0, st);
+    } else if constexpr (Tag::humanoid) {   // set_state's sim.forward() (jinja_mujoco_env.py:154) leaves data.xipos for mass_center(): a forward launch into
+      dev.aux = h->rp_rows;                 // replay scratch, then the step launch
+      rc = launch_humanoid_forward(tag, h, dev, nullptr, st);
+      if (rc == REX_OK) launch_humanoid_step(tag, h, dev, flags, action, obs_out, reward_out, done_out, nullptr, nullptr, st);
+    }
+  });
+  if (rc) return rc;
+  if ((rc = launch_timing_end(h, st, timed))) return rc;
   HIP_TRY(hipGetLastError());
   return REX_OK;
 }
@@ -714,13 +673,10 @@ extern "C" int rex_set_state(rex_t* h, const float* qpos, const float* qvel, voi
   int rc = copy_rows(h->dev.qpos, qpos, h->dims.nq, h->B, (hipStream_t)stream); if (rc) return rc;
   rc = copy_rows(h->dev.qvel, qvel, h->dims.nv, h->B, (hipStream_t)stream); if (rc) return rc;
   HIP_TRY(hipMemsetAsync(h->dev.done, 0, (size_t)h->B, (hipStream_t)stream));   // steps_beyond_done = None
-#if REX_EN_HUMANOID
-  if (h->kind == REX_HUMANOID) {   // set_state runs sim.forward(): refreshes data.xipos (jinja_mujoco_env.py:154)
-    hipLaunchKernelGGL(humanoid_forward_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), hum_lds_bytes(h), (hipStream_t)stream, h->dev, (float*)nullptr);
-    HIP_TRY(hipGetLastError());
-  }
-#endif
-  return REX_OK;
+  with_kind(h, [&](auto tag) {     // the humanoid's set_state runs sim.forward(): refreshes data.xipos (jinja_mujoco_env.py:154)
+    if constexpr (decltype(tag)::humanoid) rc = launch_humanoid_forward(tag, h, h->dev, nullptr, (hipStream_t)stream);
+  });
+  return rc;
 }
 extern "C" int rex_get_task(rex_t* h, float* xi, void* stream) {
   REX_ENTER(h, "rex_get_task");
@@ -739,30 +695,21 @@ extern "C" int rex_set_task(rex_t* h, const float* xi, void* stream) {
     rc = copy_rows(h->dev.xi + (size_t)h->dr.map[k] * h->B, xi + (size_t)k * h->B, 1, h->B, (hipStream_t)stream); if (rc) return rc;
   }
   if (rc) return rc;
-  if (h->kind == REX_WALKER2D) return launch_walker_derive(h, nullptr, 0, (hipStream_t)stream, 1);
+  if (h->kind == REX_WALKER2D) return launch_walker_derive(h, h->dev, nullptr, 0, (hipStream_t)stream, 1);
   return REX_OK;
 }
 extern "C" int rex_get_obs(rex_t* h, float* obs_out, void* stream) {
   REX_ENTER(h, "rex_get_obs");
   if (!obs_out) return set_err(REX_ERR_ARG, "rex_get_obs: null argument");
-  const dim3 g(grid_for(h)), b(lanes_of(h)); hipStream_t st = (hipStream_t)stream;
-  switch (h->kind) {
-#if REX_EN_CARTPOLE
-    case REX_CARTPOLE: hipLaunchKernelGGL(cartpole_obs_kernel, g, b, 0, st, h->dev, obs_out); break;
-#endif
-#if REX_EN_HOPPER
-    case REX_HOPPER: hipLaunchKernelGGL(planar_obs_kernel<HopperSpec>, g, b, 0, st, h->dev, obs_out); break;
-#endif
-#if REX_EN_HALFCHEETAH
-    case REX_HALFCHEETAH: hipLaunchKernelGGL(planar_obs_kernel<HalfCheetahSpec>, g, b, 0, st, h->dev, obs_out); break;
-#endif
-#if REX_EN_WALKER2D
-    case REX_WALKER2D: hipLaunchKernelGGL(planar_obs_kernel<Walker2dSpec>, g, b, 0, st, h->dev, obs_out); break;
-#endif
-#if REX_EN_HUMANOID
-    case REX_HUMANOID: hipLaunchKernelGGL(humanoid_forward_kernel, g, b, hum_lds_bytes(h), st, h->dev, obs_out); break;
-#endif
-  }
+  const dim3 g = grid_for(h), b = lanes_of(h); hipStream_t st = (hipStream_t)stream;
+  int rc = REX_OK;
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::cartpole) hipLaunchKernelGGL(cartpole_obs_kernel, g, b, 0, st, h->dev, obs_out);
+    else if constexpr (Tag::planar) hipLaunchKernelGGL(planar_obs_kernel<typename Tag::Spec>, g, b, 0, st, h->dev, obs_out);
+    else rc = launch_humanoid_forward(tag, h, h->dev, obs_out, st);
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return REX_OK;
 }
@@ -777,24 +724,13 @@ extern "C" int rex_get_counters(rex_t* h, int64_t* out) {
 }
 extern "C" int rex_get_launch_shape(const rex_t* h, int32_t* out) {
   if (!h || !out) return set_err(REX_ERR_ARG, "rex_get_launch_shape: null argument");
-  const bool planar = h->kind == REX_HOPPER || h->kind == REX_HALFCHEETAH || h->kind == REX_WALKER2D;
-  out[0] = (planar && h->pair) ? h->pair_lanes : h->lanes; out[1] = (planar && h->pair) ? 1 : 0; out[2] = (h->kind == REX_HOPPER && !h->pair && h->rolled) ? 1 : 0;
-  out[3] = (h->kind == REX_HUMANOID && h->hum_pair) ? 1 : 0;
+  report_shape(h->kind, h->shape, out);
   return REX_OK;
 }
 extern "C" int rex_set_launch_shape(rex_t* h, const int32_t* shape) {
   if (!h || !shape) return set_err(REX_ERR_ARG, "rex_set_launch_shape: null argument");
-  const bool planar = h->kind == REX_HOPPER || h->kind == REX_HALFCHEETAH || h->kind == REX_WALKER2D;
-  int lanes = shape[0] < 0 ? ((planar && h->pair) ? h->pair_lanes : h->lanes) : shape[0];
-  int pair = shape[1] < 0 ? h->pair : (shape[1] ? 1 : 0), rolled = shape[2] < 0 ? h->rolled : (shape[2] ? 1 : 0);
-  int hum_pair = shape[3] < 0 ? h->hum_pair : (shape[3] ? 1 : 0);
-  if (lanes < 8 || lanes > 64 || (lanes & (lanes - 1))) return set_err(REX_ERR_ARG, "rex_set_launch_shape: lanes must be 8, 16, 32 or 64 (got %d)", lanes);
-  if (shape[1] > 0 && !planar) return set_err(REX_ERR_ARG, "rex_set_launch_shape: two lanes per env (pair) is a shape of the planar chains");
-  if (shape[2] > 0 && h->kind != REX_HOPPER) return set_err(REX_ERR_ARG, "rex_set_launch_shape: the rolled kernel exists for the hopper only");
-  if (shape[3] > 0 && h->kind != REX_HUMANOID) return set_err(REX_ERR_ARG, "rex_set_launch_shape: hum_pair is a shape of the humanoid");
-  if (pair && rolled) return set_err(REX_ERR_ARG, "rex_set_launch_shape: the rolled kernel is a one-lane-per-env kernel (pair and rolled exclude each other)");
-  if (shape[0] >= 0) { h->lanes = lanes; h->pair_lanes = lanes; }
-  h->pair = pair; h->rolled = rolled; h->hum_pair = hum_pair;
+  const char* why = nullptr;
+  if (int rc = apply_shape_request(h->kind, shape, &h->shape, &why)) return set_err(rc, "%s", why);
   return REX_OK;
 }
 extern "C" int rex_enable_timing(rex_t* h, int enable) {
@@ -900,7 +836,7 @@ extern "C" int rex_sample_task(rex_t* h, float* xi_out, uint64_t draw_index, voi
       "sampling value of random env needs to be set before using sample_task() or set_random_task()");   // random_env.py:201
   DRParams dr = h->dr;
   for (int k = 0; k < dr.dim; k++) dr.map[k] = k;   // task order, not the kernels' full xi block
-  hipLaunchKernelGGL(sample_task_kernel, dim3(grid_for(h)), dim3(lanes_of(h)), 0, (hipStream_t)stream, h->dev, dr, (unsigned long long)draw_index, xi_out);
+  hipLaunchKernelGGL(sample_task_kernel, grid_for(h), lanes_of(h), 0, (hipStream_t)stream, h->dev, dr, (unsigned long long)draw_index, xi_out);
   HIP_TRY(hipGetLastError());
   return REX_OK;
 }

@@ -32,12 +32,13 @@ WAVE_ENVS = 64   # envs per wavefront of the step kernels at their widest (one l
 
 def shape_for_batch(kind, batch, simds=1024):
     """The launch shape rex_create picks for `batch` envs of `kind` on a GPU with `simds` SIMDs (MI355X: 1 024): the rule of
-    rex_hip.hip::create_body restated for the host (tests/test_gpu_api.py::test_launch_shape_follows_the_batch holds the two together)."""
+    csrc/launch_shape.hpp::choose_launch_shape restated for the host (tests/test_launch_shape_host.py holds the two together at every threshold
+    and for several SIMD counts without a GPU, tests/test_gpu_api.py::test_launch_shape_follows_the_batch on the card itself)."""
     planar = kind in ("hopper", "halfcheetah", "walker2d")
     pair = bool(planar and batch <= 32 * simds)
     lanes = 64 if batch > 32 * simds else 32
     if pair:   # two lanes per env: 64-lane blocks; walker2d / half-cheetah batches of >= 8 envs per SIMD halve them while the halved
-        lanes = 64   # blocks still number <= SIMDs, down to 16 lanes (pair_lanes_for)
+        lanes = 64   # blocks still number <= SIMDs, down to 16 lanes (choose_launch_shape)
         while kind != "hopper" and batch >= 8 * simds and lanes > 16 and (4 * batch + lanes - 1) // lanes <= simds:
             lanes //= 2
     return dict(lanes=lanes, pair=pair,

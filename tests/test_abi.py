@@ -49,7 +49,7 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 _CSRC = os.path.join(ROOT, "random-envs_amd", "csrc")
 _SRC = os.path.join(_CSRC, "rex_hip.hip")
 _DEVICE_WORK = re.compile(r"hipLaunchKernelGGL|hipMemcpy|hipMemset|hipDeviceSynchronize|hipEvent(Record|Create|Synchronize)|hipMalloc|hipFree|"
-                          r"\bcopy_rows\(|\bdo_reset\(|\blaunch_[a-z_]+(<[A-Za-z0-9_]+>)?\(|\bensure_replay_scratch\(")
+                          r"\bcopy_rows\(|\bdo_reset\(|\blaunch_[a-z_]+(<[A-Za-z0-9_: ]+>)?\(|\bensure_replay_scratch\(|\bwith_kind\(")
 
 
 def _exported_bodies():
@@ -135,3 +135,29 @@ def test_rex_create_has_one_cleanup_path():
     create = _exported_bodies()["rex_create"][1]
     assert "create_body(" in create and "rex_destroy(h)" in create and "*out = nullptr" in create
     assert "static bool built" not in src and "static const HumModels* m = [] {" in src
+
+
+def test_the_launch_shape_rule_and_the_kind_dispatch_exist_once():
+    """The launch-shape rule is csrc/launch_shape.hpp -- pure host code (no HIP include; the getenv test above covers its environment
+    access) that holds every threshold, while the handle keeps one LaunchShape and no loose shape field -- and rex_hip.hip asks which env
+    kinds a build compiles in with_kind, the humanoid block and the walker2d derive launch only."""
+    src = open(_SRC).read()
+    rule = open(os.path.join(_CSRC, "launch_shape.hpp")).read()
+    assert "hip" not in re.sub(r"//.*", "", rule).lower() and '#include "' not in rule.replace('#include "../../include/rex.h"', "")
+    for threshold in ("32ll * simds", "64ll * simds", "8ll * simds", "524288"):
+        assert threshold in rule, threshold
+        for p in glob.glob(os.path.join(_CSRC, "*")):
+            if os.path.isfile(p) and os.path.basename(p) != "launch_shape.hpp":
+                assert threshold not in open(p, errors="ignore").read(), (threshold, p)
+    handle = src[src.index("struct rex_env {"):src.index("constexpr size_t EV_POOL")]
+    assert "LaunchShape shape;" in handle
+    assert not re.search(r"\bint\s+(lanes|pair_lanes|pair|rolled|hum_pair|hum_fused_reset|fused_derive)\b", handle)
+    assert not re.search(r"h->(lanes|pair_lanes|pair|rolled|hum_pair|hum_fused_reset|fused_derive)\b", src)
+    dispatch = src[src.index("static void with_kind("):src.index("constexpr int DERIVE_PENDING_BIT")]
+    for kind in ("CARTPOLE", "HOPPER", "HALFCHEETAH", "WALKER2D", "HUMANOID"):
+        assert "case REX_%s:" % kind in dispatch and "REX_EN_%s" % kind in dispatch, kind
+    elsewhere = src.replace(dispatch, "")
+    assert re.findall(r"REX_EN_[A-Z0-9]+", re.sub(r"//.*", "", elsewhere)) == ["REX_EN_WALKER2D", "REX_EN_HUMANOID"]
+    assert len(re.findall(r"switch \(h->kind\)", src)) == 1
+    for name in ("launch_planar_step", "launch_humanoid_step", "launch_walker_derive", "launch_fill_rows"):
+        assert re.search(r"static (void|int) %s\(" % name, src), name
