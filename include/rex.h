@@ -313,6 +313,69 @@ int rex_rollout_gather(rex_t* h, const rex_rollout_buffers* buf, const int64_t* 
 /* out [host, 1 int64]: out-of-range sample ids rex_rollout_gather met since the last clearing read.  Synchronises. */
 int rex_rollout_read_bad_indices(rex_t* h, int64_t* out, int clear);
 
+/* ---- episode ledger: task, return and length of every finished episode, appended on the device --------------------------------
+ * What every domain-randomisation method consumes is WHICH TASK GOT WHICH RETURN (active DR, DORAEMON-style distribution updates,
+ * BayRn / SimOpt-style outer loops, return-as-a-function-of-xi evaluation).  With auto-reset and dr_training on, the rex_step launch
+ * that finishes an episode also stores the next episode's task over the lane's xi, so after rex_step the finished episode's task is
+ * gone; pairing it on the host costs a rex_get_task per step plus a data-dependent nonzero(), i.e. one synchronisation per step.  No
+ * reference counterpart of its own.  rex_step, rex_norm_* and rex_rollout_* are untouched; the ledger is an independent opt-in (it
+ * duplicates the 12 B per lane of episode totals rex_norm_* keeps).
+ *
+ * A LEDGER is an append-only table of finished episodes in caller-owned DEVICE memory, SoA over its capacity N:
+ *   task      [task_dim][N] f32  the task the episode ran under, rows in rex_get_task's order (the reduced task of the Unmodeled ids)
+ *   ep_return [N] f64            sum of the raw rewards of the episode, accumulated in fp64 in step order
+ *   ep_len    [N] i32            steps
+ *   flags     [N] u8             bit 0: the episode ended by time-limit truncation
+ *   env       [N] i64            GLOBAL env index (env_offset + lane)
+ *   step      [N] i64            serial number of the rex_eplog_step call that recorded it (0-based, counted since enable)
+ * The handle keeps per lane ep_return (f64), ep_len (i32) and a SHADOW TASK [task_dim][B] f32 -- the task in force when the lane's
+ * current episode began -- and two device words: `total` (records appended since the last clear, dropped ones included) and `serial`.
+ *
+ * rex_eplog_step reads the buffers rex_step just wrote (reward [dev, float batch], done [dev, uint8 batch], truncated [dev, uint8
+ * batch] or NULL).  For every lane i, in this order:
+ *   1. ep_return[i] += (double)reward[i];  ep_len[i] += 1.
+ *   2. if done[i] != 0:  r = number of lanes j < i with done[j] != 0, slot = total + r.  If slot < N the record (shadow task of i,
+ *      ep_return[i], ep_len[i], flags = (truncated && truncated[i]) ? 1 : 0, env_offset + i, serial) is written to `slot`; otherwise
+ *      nothing is written.  Then ep_return[i] = 0, ep_len[i] = 0 and the shadow task of i becomes the lane's CURRENT task: the next
+ *      episode's, which the step launch or the masked reset behind it has already stored.
+ *   3. after all lanes: total += number of done lanes, then serial += 1.
+ * Order: the records of one call are in env-index order and calls are in call order; the table does not depend on launch shape,
+ *   block scheduling or timing, so two runs agree bit for bit.
+ * Overflow: the earliest N records are kept, the rest are counted (rex_eplog_read).
+ * Non-finite rewards accumulate as the arithmetic gives.
+ *
+ * rex_eplog_sync: the lanes with mask[i] != 0 (all when mask == NULL) re-read their shadow task from the handle's current task;
+ *   with restart != 0 their ep_return / ep_len start again from 0.  It is the companion of rex_reset, rex_set_task,
+ *   rex_set_random_task, rex_set_state and rex_set_counters_state, in the role rex_norm_reset plays for rex_reset.  A task changed
+ *   from outside WITHOUT a sync is not seen: the episode in progress is recorded with the stale shadow task.
+ *
+ * rex_eplog_enable registers the caller's six pointers and the capacity, allocates the per-lane state and the scan scratch (one count
+ *   per block of 256 lanes: a function of the batch only), sets total = serial = 0, zeroes the totals, sets shadow = current task and
+ *   synchronises.  It is the only allocating call; calling it again re-initialises under the new buffers; every other rex_eplog_*
+ *   call before it returns REX_ERR_STATE; a NULL pointer or capacity <= 0 returns REX_ERR_ARG.
+ * rex_eplog_step is TWO launches and rex_eplog_sync ONE on `stream`; neither allocates nor synchronises, and neither keeps host-side
+ *   state that changes between calls (total and serial live on the device; no kernel argument differs from call to call).
+ *   No atomics and no waiting between blocks: the launch boundary is the barrier. */
+typedef struct rex_eplog_buffers {
+  float* task;
+  double* ep_return;
+  int32_t* ep_len;
+  uint8_t* flags;
+  int64_t* env;
+  int64_t* step;
+  int64_t capacity;
+} rex_eplog_buffers;
+int rex_eplog_enable(rex_t* h, const rex_eplog_buffers* buf);
+int rex_eplog_step(rex_t* h, const float* reward, const uint8_t* done, const uint8_t* truncated /* may be NULL */, void* stream);
+int rex_eplog_sync(rex_t* h, const uint8_t* mask, int restart, void* stream);
+/* out [host, 4 int64]: total, dropped = max(0, total - capacity), serial, capacity.  clear != 0 sets total = 0 (the next record goes
+ * to slot 0); serial keeps counting.  Synchronises. */
+int rex_eplog_read(rex_t* h, int64_t* out, int clear);
+/* the per-lane state [dev]: ep_return (double batch), ep_len (int32 batch), shadow_task (float task_dim*batch, SoA); with a drained
+ * ledger it makes a resume exact, as rex_norm_get_lane_state / rex_norm_set_lane_state do. */
+int rex_eplog_get_lane_state(rex_t* h, double* ep_return, int32_t* ep_len, float* shadow_task, void* stream);
+int rex_eplog_set_lane_state(rex_t* h, const double* ep_return, const int32_t* ep_len, const float* shadow_task, void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

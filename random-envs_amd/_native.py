@@ -21,6 +21,7 @@ SYMBOLS = [
     "rex_norm_get_lane_state", "rex_norm_set_lane_state", "rex_norm_read_episodes",
     "rex_rollout_enable", "rex_rollout_add", "rex_rollout_gae", "rex_rollout_adv_stats", "rex_rollout_get_adv_stats", "rex_rollout_gather",
     "rex_rollout_read_bad_indices",
+    "rex_eplog_enable", "rex_eplog_step", "rex_eplog_sync", "rex_eplog_read", "rex_eplog_get_lane_state", "rex_eplog_set_lane_state",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -42,6 +43,10 @@ class RexNormConfig(ctypes.Structure):
 
 class RexRolloutBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "action", "reward", "value", "log_prob", "advantage", "returns", "done")] + [("T", ctypes.c_int64)]
+
+
+class RexEplogBuffers(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("task", "ep_return", "ep_len", "flags", "env", "step")] + [("capacity", ctypes.c_int64)]
 
 
 class RexError(RuntimeError):
@@ -113,6 +118,12 @@ def lib():
     L.rex_rollout_get_adv_stats.argtypes = [vp, dp]
     L.rex_rollout_gather.argtypes = [vp, bp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.rex_rollout_read_bad_indices.argtypes = [vp, ctypes.POINTER(i64), i32]
+    L.rex_eplog_enable.argtypes = [vp, ctypes.POINTER(RexEplogBuffers)]
+    L.rex_eplog_step.argtypes = [vp, vp, vp, vp, vp]
+    L.rex_eplog_sync.argtypes = [vp, vp, i32, vp]
+    L.rex_eplog_read.argtypes = [vp, ctypes.POINTER(i64), i32]
+    L.rex_eplog_get_lane_state.argtypes = [vp, vp, vp, vp, vp]
+    L.rex_eplog_set_lane_state.argtypes = [vp, vp, vp, vp, vp]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L
