@@ -688,7 +688,9 @@ template <bool BR> REX_HD bool any_lane(bool x) { if constexpr (BR) return REX_W
 // PAIR (two lanes per env, straight-line instantiation only): SLOTS are the even slots 2g of the feet; each lane runs the
 // per-slot part of both passes for ITS end (slot 2g + parity, data kept at index 2g) and the partial gradient / Hessian /
 // line-search sums and the active-edge bits are exchanged (pair_xchg); everything else is replicated.
-template <class T, class S, bool SELF, unsigned SLOTS, bool BR, bool PAIR = false, int MAXIT = 24>
+// LAZY: the line-search sums (M sr, phi'(0), the Gauss curvature, phi' / phi'' at alpha = 1) and the carry of Ma are computed only on the
+// paths that read them -- see "line search" and "carry" in the iteration below.  Same operations on the same values, so the same bits.
+template <class T, class S, bool SELF, unsigned SLOTS, bool BR, bool PAIR = false, bool LAZY = false, int MAXIT = 24>
 REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
                                const Kin<T, S>& K, const Constraints<T, S>& C, const SelfRows<T, S>& R,
                                const LaneParams<T, S>& P, T (&qacc)[S::NV], bool warm, bool have_a0, int ls_max, int ls_free = 0, int corr = 1) {
@@ -720,12 +722,16 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
   // straight-line instantiation: hinge columns of the point Jacobians once per solve; J qacc of pass 1 is reused by pass 2
   T Jt[BR ? 1 : NC][S::NB], Jn[BR ? 1 : NC][S::NB], lt[NC], ln[NC];
   if constexpr (!BR) for_slots<SLOTS>([&](auto KK) { constexpr int k = KK; point_jac<T, S, S::geom_body[k / 2]>(K, C.px[k], C.pz[k], Jt[k], Jn[k]); });
-  T Ma[S::NV];   // M qacc: formed once, then carried along the accepted steps (Ma += alpha * M sr)
+  T Ma[S::NV];   // M qacc: formed once, then carried along the accepted steps (Ma += alpha * M sr) -- by the iteration itself when it searched,
+                 // otherwise (LAZY) at its end and only if another iteration will read it
   sym_matvec<T, S>(M, qacc, Ma);
-  bool ma_dirty = false;   // wave-uniform: a single-row correction moved qacc without updating Ma
+  bool ma_dirty = false;   // wave-uniform: a correction moved qacc without updating Ma (and, LAZY, the step before it was not carried either):
+                           // the next iteration rebuilds Ma from qacc
   constexpr int maxit = MAXIT;
-  for (int it = 0; it < maxit; ++it) {
-    if (!REX_WAVE_ANY(!lane_done)) break;
+  // ("is any lane still iterating": eager, at the top of every iteration; LAZY, once before the loop and at the end of every iteration,
+  // where the carry needs the answer anyway)
+  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; it < maxit; ++it) {
+    if constexpr (!LAZY) { if (!REX_WAVE_ANY(!lane_done)) break; }
     T cpx[NC], cpz[NC];   // per-iteration opaque copies of the contact points (see opaque())
     if constexpr (BR) for_slots<SLOTS>([&](auto KK) { constexpr int k = KK; cpx[k] = C.px[k]; cpz[k] = C.pz[k]; opaque(cpx[k]); opaque(cpz[k]); });
     if (ma_dirty) { sym_matvec<T, S>(M, qacc, Ma); ma_dirty = false; }
@@ -845,10 +851,16 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     REX_PACC(8, s_h, s_l);
     REX_MARK("pass2_ls");
     // ---- exact line search on phi(alpha); phi'(0) = g.sr, Gauss curvature sr^T M sr ----------
+    // The first `ls_free` iterations of a solve take the full Newton step without a line search (semismooth Newton: on
+    // this piecewise-quadratic cost it usually finds the active set in as many iterations as with the exact search, and
+    // every evaluation of phi' costs a pass over all rows); from then on the exact search, which guarantees descent,
+    // takes over -- a solve that has not converged by then is a hard one (cycling active sets).
+    // An iteration that does not search reads nothing of phi but the rows active at alpha = 1 (exact_step, the correction):
+    // LAZY leaves M sr, q1 / q2 / d0, d1ref and the phi' / phi'' sums (with their pair exchanges) to the iterations that search.
+    // (wave-uniform and scalar: `it` and both parameters are)
+    const bool want_ls = !LAZY || (it >= ls_free && ls_max > 0);
     T Ms[S::NV];
-    sym_matvec<T, S>(M, sr, Ms);
-    T q1 = T(0), q2 = T(0), d0 = T(0);
-    static_for<0, S::NV>([&](auto II) { q1 += sr[II] * (Ma[II] - qfrc_smooth[II]); q2 += sr[II] * Ms[II]; d0 += sr[II] * g[II]; });
+    T q1 = T(0), q2 = T(0);
     unsigned m_lim, m_e1, m_e2, m_e3, m_self;   // rows active at the last evaluated alpha
     // every row is linear in alpha: x(alpha) = r + alpha v with r = J qacc - aref, v = J sr.  The slot products J qacc, J sr
     // are formed once per Newton iteration; an evaluation of phi' is then a few multiply-adds per slot.
@@ -860,17 +872,19 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
         if (REX_WAVE_ANY((C.con_mask >> k) & 1u)) jdot2<T, S, b>(K, cpx[k], cpz[k], qacc, sr, lt[k], ln[k], lvt[k], lvn[k]);
       } else jdot_pre<T, S, b>(Jt[k], Jn[k], sr, lvt[k], lvn[k]);   // J qacc: lt / ln of pass 1
     });
-    auto deriv = [&](T a, T& d1, T& d2) {
+    // SUMS = IC<0>: only the rows active at a (an iteration that does not search)
+    auto deriv = [&](auto SUMS, T a, T& d1, T& d2) {
+      constexpr bool sums = int(SUMS) != 0;
       REX_COUNT(ls_evals, 1);
       REX_MARK("deriv");
       m_lim = m_e1 = m_e2 = m_e3 = m_self = 0u;
-      d1 = q1 + a * q2; d2 = q2;
+      if constexpr (sums) { d1 = q1 + a * q2; d2 = q2; }
       static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ;
         if constexpr (S::limited[j]) {
           T lr = C.lsig[j] * qacc[j + 2] - C.laref[j], lv = C.lsig[j] * sr[j + 2];
           T x = lr + a * lv; bool on = ((C.lim_mask >> j) & 1u) && x < T(0);
           if (on) m_lim |= 1u << j;
-          T dd = on ? C.lD[j] : T(0); d1 += dd * x * lv; d2 += dd * lv * lv; } });
+          if constexpr (sums) { T dd = on ? C.lD[j] : T(0); d1 += dd * x * lv; d2 += dd * lv * lv; } } });
       T d1s = T(0), d2s = T(0);   // PAIR: this lane's slot part of phi', phi''
       for_slots<SLOTS>([&](auto KK) {
         {
@@ -884,14 +898,16 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
             T x0 = r0 + a * v0, x1 = r1 + a * v1, x2 = r2 + a * v2;
             const bool o0 = act && x0 < T(0), o1 = act && x1 < T(0), o2 = act && x2 < T(0);
             if (o0) m_e1 |= 1u << (k + par); if (o1) m_e2 |= 1u << (k + par); if (o2) m_e3 |= 1u << (k + par);
-            T w0 = o0 ? C.D[k] : T(0), w1 = o1 ? C.D[k] : T(0), w2 = o2 ? T(2) * C.D[k] : T(0);
-            if constexpr (PAIR) { d1s += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2s += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2; }
-            else { d1 += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2 += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2; }
+            if constexpr (sums) {
+              T w0 = o0 ? C.D[k] : T(0), w1 = o1 ? C.D[k] : T(0), w2 = o2 ? T(2) * C.D[k] : T(0);
+              if constexpr (PAIR) { d1s += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2s += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2; }
+              else { d1 += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2 += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2; }
+            }
           }
         }
       });
       if constexpr (PAIR) {
-        d1 += d1s + pair_xchg(d1s); d2 += d2s + pair_xchg(d2s);
+        if constexpr (sums) { d1 += d1s + pair_xchg(d1s); d2 += d2s + pair_xchg(d2s); }
         m_e1 |= pair_xchg(m_e1); m_e2 |= pair_xchg(m_e2); m_e3 |= pair_xchg(m_e3);
       }
       if constexpr (SELF && S::NSELF > 0) static_for<0, 2 * S::NSELF>([&](auto PP) {
@@ -903,32 +919,37 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
           T r = R.nx[p] * (tb - ta) + R.nz[p] * (nb - na) - R.aref[p], vv = R.nx[p] * (ub - ua) + R.nz[p] * (mb_ - ma_);
           T x = r + a * vv; const bool on = act && x < T(0);
           if (on) m_self |= 1u << p;
-          T dd = on ? R.D[p] : T(0);
-          d1 += dd * x * vv; d2 += dd * vv * vv;
+          if constexpr (sums) { T dd = on ? R.D[p] : T(0); d1 += dd * x * vv; d2 += dd * vv * vv; }
         }
       });
     };
     // the Newton step itself (alpha = 1) is exact whenever the active set does not change along it
-    const T d1ref = abs_t(d0) * T(sizeof(T) == 4 ? 1e-5 : 1e-13) + T(1e-30);
-    T a = T(1), lo = T(0), hi = T(-1), d1, d2;
-    deriv(a, d1, d2);
-    bool ls_done = lane_done || abs_t(d1) <= d1ref;
-    // The first `ls_free` iterations of a solve take the full Newton step without a line search (semismooth Newton: on
-    // this piecewise-quadratic cost it usually finds the active set in as many iterations as with the exact search, and
-    // every evaluation of phi' costs a pass over all rows); from then on the exact search, which guarantees descent,
-    // takes over -- a solve that has not converged by then is a hard one (cycling active sets).
-    const int ls_cap = it < ls_free ? 0 : ls_max;
-    for (int ls = 0; ls < ls_cap; ++ls) {   // phi' is piecewise linear and increasing: safeguarded Newton
-      if (!REX_WAVE_ANY(!ls_done)) break;
-      if (d1 < T(0)) lo = a; else hi = a;
-      T an_ = a - d1 * rcp_t(d2);
-      if (hi >= T(0) && (an_ <= lo || an_ >= hi)) an_ = T(0.5) * (lo + hi);
-      an_ = max_t(an_, lo);
-      T prev = a;
-      a = ls_done ? a : an_;
-      deriv(a, d1, d2);
-      ls_done = ls_done || abs_t(d1) <= d1ref || a == prev;
-    }
+    T a = T(1), d1 = T(0), d2 = T(0);
+    if (want_ls) {
+      sym_matvec<T, S>(M, sr, Ms);
+      T d0 = T(0);
+      static_for<0, S::NV>([&](auto II) { q1 += sr[II] * (Ma[II] - qfrc_smooth[II]); q2 += sr[II] * Ms[II]; d0 += sr[II] * g[II]; });
+      const T d1ref = abs_t(d0) * T(sizeof(T) == 4 ? 1e-5 : 1e-13) + T(1e-30);
+      T lo = T(0), hi = T(-1);
+      deriv(IC<1>{}, a, d1, d2);
+      bool ls_done = lane_done || abs_t(d1) <= d1ref;
+      const int ls_cap = it < ls_free ? 0 : ls_max;
+      for (int ls = 0; ls < ls_cap; ++ls) {   // phi' is piecewise linear and increasing: safeguarded Newton
+        if (!REX_WAVE_ANY(!ls_done)) break;
+        if (d1 < T(0)) lo = a; else hi = a;
+        T an_ = a - d1 * rcp_t(d2);
+        if (hi >= T(0) && (an_ <= lo || an_ >= hi)) an_ = T(0.5) * (lo + hi);
+        an_ = max_t(an_, lo);
+        T prev = a;
+        a = ls_done ? a : an_;
+        deriv(IC<1>{}, a, d1, d2);
+        ls_done = ls_done || abs_t(d1) <= d1ref || a == prev;
+      }
+      if constexpr (LAZY) {
+        const T ac = lane_done ? T(0) : a;   // (the step the update below takes)
+        static_for<0, S::NV>([&](auto II) { Ma[II] += ac * Ms[II]; });
+      }
+    } else deriv(IC<0>{}, a, d1, d2);
     REX_PSTAMP(s_d, d1 + d2 + a);
     REX_PACC(9, s_l, s_d);
     REX_MARK("pass2_update");
@@ -937,8 +958,18 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     const bool exact_step = a == T(1) && m_lim == lim_on && m_e1 == e1 && m_e2 == e2 && m_e3 == e3 && m_self == self_on;
     a = lane_done ? T(0) : a;
     T amax = T(0), smax = T(0);
-    static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; Ma[II] += a * Ms[II]; amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
+    static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; if constexpr (!LAZY) Ma[II] += a * Ms[II];
+                                        amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);   // stagnation at rounding level
+    // carry (LAZY, after an iteration that did not search): Ma += a M sr, taken only where a further iteration reads it -- not when the wave is
+    // done, and not before a correction (ma_dirty rebuilds Ma then, so `sr` and `a` are dead across that block)
+    bool go = true;   // LAZY: wave-uniform, some lane is still iterating
+    auto carry = [&]() {
+      if constexpr (LAZY) {
+        go = REX_WAVE_ANY(!lane_done);
+        if (go && !want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
+      }
+    };
     REX_PSTAMP(s_u, qacc[0] + amax + smax);
     REX_PACC(10, s_d, s_u);
     // ---- one-group correction (straight-line instantiation) ---------------------------------------------------------
@@ -1018,12 +1049,14 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3;
         ma_dirty = true;
         REX_COUNT(nocon, 1);   // (diagnostic builds: slot "nocon" counts the correction trips of the wave)
-      }
-    }
+        if constexpr (LAZY) go = REX_WAVE_ANY(!lane_done);
+      } else carry();
+    } else carry();
     REX_PSTAMP(s_2, qacc[0] + amax);
     REX_PACC(6, s_1, s_2); REX_PACC(11, s_u, s_2);
     st.iters = it + 1;
-    if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done);
+    if constexpr (LAZY) { if (it == MAXIT - 1) st.capped = go; if (!go) break; }
+    else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
   }
   return st;
 }
@@ -1295,7 +1328,7 @@ REX_HD void list_store(const Constraints<T, S>& C, const LaneParams<T, S>& P, co
     q[LM::off(SF_PX)] = C.px[k]; q[LM::off(SF_PZ)] = C.pz[k]; q[LM::off(SF_D)] = C.D[k]; q[LM::off(SF_AN)] = C.an[k]; q[LM::off(SF_AT)] = C.at[k];
     q[LM::off(SF_MU)] = P.mu[g]; });
 }
-template <class T, class S, bool SELF, bool PAIR, int MAXIT = 24>
+template <class T, class S, bool SELF, bool PAIR, bool LAZY = false, int MAXIT = 24>   // LAZY: see solve_newton
 REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
                                     const Kin<T, S>& K, const Constraints<T, S>& C, unsigned self_mask, const SlotMem<T, S, PAIR>& L,
                                     T (&qacc)[S::NV], bool warm, bool have_a0, int ls_max, int ls_free, int corr) {
@@ -1331,8 +1364,8 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
   T Ma[S::NV];
   sym_matvec<T, S>(M, qacc, Ma);
   bool ma_dirty = false;
-  for (int it = 0; it < MAXIT; ++it) {
-    if (!REX_WAVE_ANY(!lane_done)) break;
+  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; it < MAXIT; ++it) {   // (loop control: see solve_newton)
+    if constexpr (!LAZY) { if (!REX_WAVE_ANY(!lane_done)) break; }
     // A later iteration walks the units / capsule-capsule rows of the lanes that are STILL ITERATING only: a wave repeats a pass for one or two
     // of its lanes, and the pass costs per listed unit.  (A unit another lane owns adds exact zeros to this lane's sums: same bits either way.)
     // Measured (step kernel, 32 768 envs): half-cheetah 0.1031 -> 0.0956 ms, C3 0.1008 -> 0.0940, walker2d 0.1981 -> 0.1931; the hopper, whose waves
@@ -1450,22 +1483,28 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
       }
     }
     // ---- line search on phi(alpha): J sr of every listed unit into the column and phi'(1) in the same walk ------------------------------------
+    // (an iteration that does not search only needs the rows active at alpha = 1, and J sr in the column for the correction and for a later
+    // search: LAZY leaves the sums to the iterations that search -- solve_newton)
+    const bool want_ls = !LAZY || (it >= ls_free && ls_max > 0);
     T Ms[S::NV];
-    sym_matvec<T, S>(M, sr, Ms);
     T q1 = T(0), q2 = T(0), d0 = T(0);
-    static_for<0, S::NV>([&](auto II) { q1 += sr[II] * (Ma[II] - qfrc_smooth[II]); q2 += sr[II] * Ms[II]; d0 += sr[II] * g[II]; });
+    if (want_ls) {
+      sym_matvec<T, S>(M, sr, Ms);
+      static_for<0, S::NV>([&](auto II) { q1 += sr[II] * (Ma[II] - qfrc_smooth[II]); q2 += sr[II] * Ms[II]; d0 += sr[II] * g[II]; });
+    }
     unsigned m_lim, m_e1, m_e2, m_e3, m_self;
-    // phi'(a), phi''(a) without the units' part, and the limit / self rows active at a
-    auto deriv_head = [&](T a, T& d1, T& d2) {
+    // phi'(a), phi''(a) without the units' part, and the limit / self rows active at a  (SUMS = IC<0>: the active rows only)
+    auto deriv_head = [&](auto SUMS, T a, T& d1, T& d2) {
+      constexpr bool sums = int(SUMS) != 0;
       REX_COUNT(ls_evals, 1);
       m_lim = m_e1 = m_e2 = m_e3 = m_self = 0u;
-      d1 = q1 + a * q2; d2 = q2;
+      if constexpr (sums) { d1 = q1 + a * q2; d2 = q2; }
       static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ;
         if constexpr (S::limited[j]) {
           T lr = C.lsig[j] * qacc[j + 2] - C.laref[j], lv = C.lsig[j] * sr[j + 2];
           T x = lr + a * lv; bool on = ((C.lim_mask >> j) & 1u) && x < T(0);
           if (on) m_lim |= 1u << j;
-          T dd = on ? C.lD[j] : T(0); d1 += dd * x * lv; d2 += dd * lv * lv; } });
+          if constexpr (sums) { T dd = on ? C.lD[j] : T(0); d1 += dd * x * lv; d2 += dd * lv * lv; } } });
       if constexpr (SELF && S::NSELF > 0) {
         for (unsigned m = ums; m; m &= m - 1u) {
           const unsigned r = (unsigned)__builtin_ctz(m);
@@ -1473,31 +1512,32 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
           const T vv = q[LM::soff(SR_JV)], x = q[LM::soff(SR_JQ)] - q[LM::soff(SR_AREF)] + a * vv;
           const bool on = ((R.mask >> r) & 1u) && x < T(0);
           m_self |= on ? (1u << r) : 0u;
-          const T dd = on ? q[LM::soff(SR_D)] : T(0);
-          d1 += dd * x * vv; d2 += dd * vv * vv;
+          if constexpr (sums) { const T dd = on ? q[LM::soff(SR_D)] : T(0); d1 += dd * x * vv; d2 += dd * vv * vv; }
         }
       }
     };
     // one unit's part of phi', phi'' and of the sets at a, from (J qacc, J sr)
-    auto deriv_unit = [&](T a, unsigned b, bool act, T D, T an, T at, T mu, T jt, T jn, T vt, T vn, T& d1s, T& d2s) {
+    auto deriv_unit = [&](auto SUMS, T a, unsigned b, bool act, T D, T an, T at, T mu, T jt, T jn, T vt, T vn, T& d1s, T& d2s) {
       const T r0 = jn + mu * jt - (an + at), r1 = jn - mu * jt - (an - at), r2 = jn - an;
       const T v0 = vn + mu * vt, v1 = vn - mu * vt, v2 = vn;
       const T x0 = r0 + a * v0, x1 = r1 + a * v1, x2 = r2 + a * v2;
       const bool o0 = act && x0 < T(0), o1 = act && x1 < T(0), o2 = act && x2 < T(0);
       m_e1 |= o0 ? (1u << b) : 0u; m_e2 |= o1 ? (1u << b) : 0u; m_e3 |= o2 ? (1u << b) : 0u;
-      const T w0 = o0 ? D : T(0), w1 = o1 ? D : T(0), w2 = o2 ? T(2) * D : T(0);
-      d1s += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2s += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2;
+      if constexpr (int(SUMS) != 0) {
+        const T w0 = o0 ? D : T(0), w1 = o1 ? D : T(0), w2 = o2 ? T(2) * D : T(0);
+        d1s += w0 * x0 * v0 + w1 * x1 * v1 + w2 * x2 * v2; d2s += w0 * v0 * v0 + w1 * v1 * v1 + w2 * v2 * v2;
+      }
     };
-    auto deriv_tail = [&](T& d1, T& d2, T d1s, T d2s) {
+    auto deriv_tail = [&](auto SUMS, T& d1, T& d2, T d1s, T d2s) {
+      constexpr bool sums = int(SUMS) != 0;
       if constexpr (PAIR) {
-        d1 += d1s + pair_xchg(d1s); d2 += d2s + pair_xchg(d2s);
+        if constexpr (sums) { d1 += d1s + pair_xchg(d1s); d2 += d2s + pair_xchg(d2s); }
         m_e1 |= pair_xchg(m_e1); m_e2 |= pair_xchg(m_e2); m_e3 |= pair_xchg(m_e3);
-      } else { d1 += d1s; d2 += d2s; }
+      } else if constexpr (sums) { d1 += d1s; d2 += d2s; }
     };
-    const T d1ref = abs_t(d0) * T(sizeof(T) == 4 ? 1e-5 : 1e-13) + T(1e-30);
-    T a = T(1), lo = T(0), hi = T(-1), d1, d2;
-    {
-      deriv_head(a, d1, d2);
+    T a = T(1), d1 = T(0), d2 = T(0);
+    auto first_walk = [&](auto SUMS) {   // J sr of every listed unit into the column; phi' / the active rows at alpha = 1
+      deriv_head(SUMS, a, d1, d2);
       T d1s = T(0), d2s = T(0);
       for (unsigned m = um; m; m &= m - 1u) {
         const unsigned u = (unsigned)__builtin_ctz(m);
@@ -1511,40 +1551,57 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
           list_jac<T, S, SUB>(K, px, pz, anc, jt, jn);
           T vt, vn; list_dot<T, S, SUB>(jt, jn, sr, vt, vn);
           q[LM::off(SF_LVT)] = vt; q[LM::off(SF_LVN)] = vn;
-          deriv_unit(a, b, act, D, an, at, mu, t, n, vt, vn, d1s, d2s); });
+          deriv_unit(SUMS, a, b, act, D, an, at, mu, t, n, vt, vn, d1s, d2s); });
       }
-      deriv_tail(d1, d2, d1s, d2s);
-    }
+      deriv_tail(SUMS, d1, d2, d1s, d2s);
+    };
+    if (want_ls) first_walk(IC<1>{}); else first_walk(IC<0>{});
     auto deriv = [&](T aa, T& dd1, T& dd2) {   // phi' at another alpha: everything it needs is in the column
-      deriv_head(aa, dd1, dd2);
+      deriv_head(IC<1>{}, aa, dd1, dd2);
       T d1s = T(0), d2s = T(0);
       for (unsigned m = um; m; m &= m - 1u) {
         const unsigned u = (unsigned)__builtin_ctz(m);
         const T* q = L.unit(u);
         const unsigned b = bit_of(u);
-        deriv_unit(aa, b, (C.con_mask >> b) & 1u, q[LM::off(SF_D)], q[LM::off(SF_AN)], q[LM::off(SF_AT)], q[LM::off(SF_MU)],
+        deriv_unit(IC<1>{}, aa, b, (C.con_mask >> b) & 1u, q[LM::off(SF_D)], q[LM::off(SF_AN)], q[LM::off(SF_AT)], q[LM::off(SF_MU)],
                    q[LM::off(SF_LT)], q[LM::off(SF_LN)], q[LM::off(SF_LVT)], q[LM::off(SF_LVN)], d1s, d2s);
       }
-      deriv_tail(dd1, dd2, d1s, d2s);
+      deriv_tail(IC<1>{}, dd1, dd2, d1s, d2s);
     };
-    bool ls_done = lane_done || abs_t(d1) <= d1ref;
-    const int ls_cap = it < ls_free ? 0 : ls_max;
-    for (int ls = 0; ls < ls_cap; ++ls) {
-      if (!REX_WAVE_ANY(!ls_done)) break;
-      if (d1 < T(0)) lo = a; else hi = a;
-      T an_ = a - d1 * rcp_t(d2);
-      if (hi >= T(0) && (an_ <= lo || an_ >= hi)) an_ = T(0.5) * (lo + hi);
-      an_ = max_t(an_, lo);
-      T prev = a;
-      a = ls_done ? a : an_;
-      deriv(a, d1, d2);
-      ls_done = ls_done || abs_t(d1) <= d1ref || a == prev;
+    if (want_ls) {
+      const T d1ref = abs_t(d0) * T(sizeof(T) == 4 ? 1e-5 : 1e-13) + T(1e-30);
+      T lo = T(0), hi = T(-1);
+      bool ls_done = lane_done || abs_t(d1) <= d1ref;
+      const int ls_cap = it < ls_free ? 0 : ls_max;
+      for (int ls = 0; ls < ls_cap; ++ls) {
+        if (!REX_WAVE_ANY(!ls_done)) break;
+        if (d1 < T(0)) lo = a; else hi = a;
+        T an_ = a - d1 * rcp_t(d2);
+        if (hi >= T(0) && (an_ <= lo || an_ >= hi)) an_ = T(0.5) * (lo + hi);
+        an_ = max_t(an_, lo);
+        T prev = a;
+        a = ls_done ? a : an_;
+        deriv(a, d1, d2);
+        ls_done = ls_done || abs_t(d1) <= d1ref || a == prev;
+      }
+      if constexpr (LAZY) {
+        const T ac = lane_done ? T(0) : a;   // (the step the update below takes)
+        static_for<0, S::NV>([&](auto II) { Ma[II] += ac * Ms[II]; });
+      }
     }
     const bool exact_step = a == T(1) && m_lim == lim_on && m_e1 == e1 && m_e2 == e2 && m_e3 == e3 && m_self == self_on;
     a = lane_done ? T(0) : a;
     T amax = T(0), smax = T(0);
-    static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; Ma[II] += a * Ms[II]; amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
+    static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; if constexpr (!LAZY) Ma[II] += a * Ms[II];
+                                        amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);
+    bool go = true;   // LAZY: wave-uniform, some lane is still iterating
+    auto carry = [&]() {   // (solve_newton: the carry of Ma after an iteration that did not search, only where another iteration reads it)
+      if constexpr (LAZY) {
+        go = REX_WAVE_ANY(!lane_done);
+        if (go && !want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
+      }
+    };
     // ---- one-group correction (see solve_newton): one joint limit or the edges of ONE unit toggled along a full step ----------------------
     {
       REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
@@ -1627,10 +1684,12 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3; p_self = can ? m_self : p_self;
         ma_dirty = true;
         REX_COUNT(nocon, 1);
-      }
+        if constexpr (LAZY) go = REX_WAVE_ANY(!lane_done);
+      } else carry();
     }
     st.iters = it + 1;
-    if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done);
+    if constexpr (LAZY) { if (it == MAXIT - 1) st.capped = go; if (!go) break; }
+    else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
   }
   return st;
 }
@@ -1643,6 +1702,15 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
                           const LaneParams<T, S>& P, const SolParams<T>& sp, T (&qacc)[S::NV], T (&M)[S::NV][S::NV],
                           bool warm = false, T* slot_mem = nullptr) {
   constexpr bool ROLLED = GEN == 1;
+  // Which instantiations compute the line-search sums lazily (solve_newton, LAZY).  Device: the two-lanes-per-env kernels (feet-only path and list
+  // solver).  The one-lane kernels stay eager: the second, sets-only copy of deriv() costs the 458-register hopper kernel registers, and the
+  // rolled solver rebuilds Ma every iteration anyway.  Host builds run every unrolled / list instantiation lazily: same bits either way, and
+  // that is what the CPU tests check (tests/golden/planar_fp32_bits.npz was recorded from the eager code).
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool LAZY = PAIR;
+#else
+  constexpr bool LAZY = true;
+#endif
   REX_STAMP(t_0);
   REX_MARK("kinematics");
   REX_PSTAMP(p_0, q[0]);
@@ -1713,10 +1781,10 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
     if constexpr (PAIR) {   // two lanes per env: each lane its own end of the feet (even slot 2g holds the own end's data)
       constexpr unsigned FASTP = FAST & 0x55555555u;
       slot_rows<T, S, FASTP, false, true>(v, G, P, sp, K, C);
-      st = solve_newton<T, S, false, FASTP, false, true>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
+      st = solve_newton<T, S, false, FASTP, false, true, LAZY>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     } else {
       slot_rows<T, S, FAST, false>(v, G, P, sp, K, C);
-      st = solve_newton<T, S, false, FAST, false>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
+      st = solve_newton<T, S, false, FAST, false, false, LAZY>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     }
   }
   else if (GEN == 2 && (mode == 1 || mode == 2)) {   // the LIST solver: one instantiation for both modes (a lane without self rows has R.mask == 0)
@@ -1731,7 +1799,7 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
 #endif
       list_store<T, S, PAIR>(C, P, L);
       if (mode == 2) list_store_self<T, S, PAIR>(R, L);   // (mode 1: R.mask == 0 in every lane, nothing of R is read)
-      st = solve_newton_list<T, S, (S::NSELF > 0), PAIR>(M, f, a0, K, C, R.mask, L, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
+      st = solve_newton_list<T, S, (S::NSELF > 0), PAIR, LAZY>(M, f, a0, K, C, R.mask, L, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     }
   } else if (ROLLED && (mode == 1 || mode == 2)) {   // (one call site for both: the row list carries the self rows when there are any)
     if constexpr (ROLLED) {
@@ -1743,12 +1811,12 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
     }
   } else if (mode == 2) {
     if constexpr (PAIR) detect_constraints<T, S, false>(q, v, G, sp, K, C);   // the general instantiations run replicated in both lanes of a pair: every slot
-    if constexpr (S::NSELF > 0 && GEN == 0) { slot_rows<T, S, ALL, true>(v, G, P, sp, K, C); st = solve_newton<T, S, true, ALL, true>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr); }
+    if constexpr (S::NSELF > 0 && GEN == 0) { slot_rows<T, S, ALL, true>(v, G, P, sp, K, C); st = solve_newton<T, S, true, ALL, true, false, LAZY>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr); }
   } else if (mode == 1) {
     if constexpr (GEN == 0) {
       if constexpr (PAIR) detect_constraints<T, S, false>(q, v, G, sp, K, C);
       slot_rows<T, S, ALL, true>(v, G, P, sp, K, C);
-      st = solve_newton<T, S, false, ALL, true>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
+      st = solve_newton<T, S, false, ALL, true, false, LAZY>(M, f, a0, K, C, R, P, qacc, warm, have_a0, sp.ls_max, sp.ls_free, sp.corr);
     }
   }
   else static_for<0, S::NV>([&](auto II) { qacc[II] = a0[II]; });
