@@ -1,7 +1,9 @@
 // humanoid_kernels.hpp -- kernels of the humanoid (random_envs/jinja/random_humanoid.py).
 //
 // The default step is humanoid_pair_step_kernel: TWO LANES PER ENV (humanoid_pair.hpp; 32 envs per 64-lane block, every lane active), the
-// env's dual PGS working set and hit queue in one LDS column, the auto-reset of finished envs fused into the launch.  humanoid_step_kernel
+// env's dual PGS working set and hit queue in one LDS column, the auto-reset of finished envs fused into the launch.  Its body is four
+// calls into humanoid_pair.hpp -- load_lane, env_step, store_lane, reset_lane: which lane holds which row of the state is said there, once,
+// and the host harness runs the same functions -- plus what is not layout: Philox set-up, done logic, counters, outputs.  humanoid_step_kernel
 // is the hum_pair = 0 shape (REX_HUM_PAIR=0): one env per lane over humanoid_engine.hpp, which the reset and forward kernels use at every
 // setting.  There the per-lane working set of a forward evaluation (hum::Scratch, ~20 KB: M 23x23, J and M^-1 J^T for up to 64 rows) lives
 // in HIP scratch memory, lane-interleaved so every access of a wave is one coalesced segment.  The compiled model is uniform and sits in
@@ -20,6 +22,13 @@ __device__ __forceinline__ void hum_lane(const DevState& s, unsigned i, hum::Lan
   for (int k = 0; k < 13; k++) L.mass[1 + k] = (s.xi + (size_t)k * s.B)[i];
   for (int d = 0; d < 6; d++) L.damping[d] = 0.0f;
   for (int k = 0; k < 17; k++) L.damping[6 + k] = (s.xi + (size_t)(13 + k) * s.B)[i];
+}
+
+// the 45 normals of an observation (noise only on the qpos / qvel slices, random_humanoid.py:193-204) from the stream at `offset`
+__device__ __forceinline__ void hum_obs_noise(const DevState& s, const StepFlags& fl, unsigned i, unsigned long long offset, float (&nz)[45]) {
+  rocrand_state_philox4x32_10 st;
+  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), offset, &st);
+  for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st);
 }
 
 __global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags fl, const float* __restrict__ action,
@@ -107,24 +116,13 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
   const bool left = (lane & 1u) != 0u;
   const size_t B = (size_t)s.B;
   const DevPair p;
-  // set_task (random_humanoid.py:156-158): body_mass[1:] = xi[:13]; dof_damping[6:] = xi[13:] -- this lane's 8 bodies / 16 dofs
+  // this env's element of a row of the SoA state; WHICH rows a lane reads and writes is humanoid_pair.hpp's load_lane / store_lane
+  auto rd = [&](int blk, int row) { return ((blk == pr::XI ? s.xi : blk == pr::QPOS ? s.qpos : blk == pr::QVEL ? s.qvel : blk == pr::ACTION ? action : s.aux) + (size_t)row * B)[i]; };
+  auto wr = [&](int blk, int row, float val) { ((blk == pr::QPOS ? s.qpos : blk == pr::QVEL ? s.qvel : s.aux) + (size_t)row * B)[i] = val; };
   pr::PLane<float> L;
-  static_for<0, pr::LB>([&](auto BB) { constexpr int lb = BB; L.mass[lb] = (s.xi + (size_t)((left ? pr::gbL(lb) : pr::gbR(lb)) - 1) * B)[i]; });
-  static_for<0, pr::LD>([&](auto DD) { constexpr int ld = DD;
-    if constexpr (ld < 6) L.damping[ld] = 0.0f; else L.damping[ld] = (s.xi + (size_t)(13 + (left ? pr::gdL(ld) : pr::gdR(ld)) - 6) * B)[i]; });
   float ql[pr::LQ], vl[pr::LD], cl[pr::LU], xp[pr::LB];
-  static_for<0, 7>([&](auto KK) { constexpr int k = KK; ql[k] = (s.qpos + (size_t)k * B)[i]; });
-  static_for<6, pr::LD>([&](auto DD) { constexpr int ld = DD; ql[ld + 1] = (s.qpos + (size_t)((left ? pr::gdL(ld) : pr::gdR(ld)) + 1) * B)[i]; });
-  static_for<0, pr::LD>([&](auto DD) { constexpr int ld = DD; vl[ld] = (s.qvel + (size_t)(left ? pr::gdL(ld) : pr::gdR(ld)) * B)[i]; });
-  static_for<6, pr::LD>([&](auto DD) { constexpr int ld = DD;     // data.ctrl holds the raw action (:167); motor u drives dof kActDof[u]
-    constexpr int uR = ld == 6 ? 1 : ld == 7 ? 0 : ld == 8 ? 2 : ld < 13 ? 3 + (ld - 9) : 11 + (ld - 13);
-    constexpr int uL = ld < 9 ? uR : ld < 13 ? 7 + (ld - 9) : 14 + (ld - 13);
-    cl[ld - 6] = (action + (size_t)(left ? uL : uR) * B)[i]; });
-  static_for<0, pr::LB>([&](auto BB) { constexpr int lb = BB; xp[lb] = (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i]; });
-  float asq_side = 0.0f, asq = 0.0f;
-  static_for<0, 3>([&](auto KK) { asq += cl[KK] * cl[KK]; });
-  static_for<3, pr::LU>([&](auto KK) { asq_side += cl[KK] * cl[KK]; });
-  asq += pr::psum(p, asq_side);
+  pr::load_lane(left, rd, L, ql, vl, cl, xp);
+  const float asq = pr::ctrl_sq(p, cl);
   pr::PKin<float> kn; pr::PScratch<float> sc; pr::PObs<float> park;
   REX_HCLEAR(kn);   // (probes.hpp: empty in the product build)
   const int t = s.t[i] + 1;
@@ -134,18 +132,17 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
   REX_WWAVE_DONE(tk0); REX_HFLUSH(kn);
   // observation (random_humanoid.py:193-204); noise only on the qpos / qvel slices: the 45 draws in row order, as one lane per env made them
   float nz[45];
-  if (fl.noisy) {
-    rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, &st);
-    for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st);
-  }
-  pr::emit_obs(p, ql, vl, park, [&](auto RR, auto RL, float val) {
-    constexpr int rr = RR, rl = RL;
-    if constexpr (rr < 45 && rl < 45) { if (fl.noisy) val += left ? nz[rl] : nz[rr]; }
-    const size_t row = left ? (size_t)rl : (size_t)rr;
-    (obs + row * B)[i] = val;
-    if (term_obs) (term_obs + row * B)[i] = val;
-  });
+  auto put_obs = [&](float* dst, float* dst2) {
+    pr::emit_obs(p, ql, vl, park, [&](auto RR, auto RL, float val) {
+      constexpr int rr = RR, rl = RL;
+      if constexpr (rr < 45 && rl < 45) { if (fl.noisy) val += left ? nz[rl] : nz[rr]; }
+      const size_t row = left ? (size_t)rl : (size_t)rr;
+      (dst + row * B)[i] = val;
+      if (dst2) (dst2 + row * B)[i] = val;
+    });
+  };
+  if (fl.noisy) hum_obs_noise(s, fl, i, (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, nz);
+  put_obs(obs, term_obs);
   bool finite = true;
   static_for<0, pr::LQ>([&](auto KK) { finite = finite && isfinite(ql[KK]); });
   static_for<0, pr::LD>([&](auto KK) { finite = finite && isfinite(vl[KK]); });
@@ -154,20 +151,12 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
   if (fl.endless && finite) dn = false;
   const bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;
   const bool d = dn || trunc;
-  if (!fl.readonly) {   // (rex_replay: nothing of the handle is written, its counters included)
-    static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD; const size_t g = left ? pr::gdL(ld) : pr::gdR(ld);
-      (s.qpos + (g + 1) * B)[i] = ql[ld + 1]; (s.qvel + g * B)[i] = vl[ld]; });
-    static_for<3, pr::LB>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i] = xp[lb]; });
-  }
+  if (!fl.readonly) pr::store_lane(left, wr, ql, vl, xp);   // (rex_replay: nothing of the handle is written, its counters included)
   if (!left) {
     if (!fl.readonly) {
       if (!finite) atomicAdd(s.counters + 0, 1ull);
       if (kn.overflow) atomicAdd(s.counters + 3, 1ull);
       s.t[i] = t;
-      static_for<0, 10>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = ql[k]; });
-      static_for<0, 9>([&](auto KK) { constexpr int k = KK; (s.qvel + (size_t)k * B)[i] = vl[k]; });
-      static_for<0, 3>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(lb + 1) * B)[i] = xp[lb]; });
-      s.aux[i] = 0.0f;                                                // world body
       s.done[i] = d ? 2 : 0;
     }
     if (fl.info) for (int k = 0; k < 4; k++) (fl.info + k * B)[i] = terms[k];   // reward_linvel, _quadctrl, _alive, _impact (random_humanoid.py:182-187)
@@ -177,50 +166,17 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
   // Auto-reset fused into the step launch (the masked reset launch behind every step was 80 us of a 1.77 ms step): a finished env
   // restarts here, both lanes of its pair.  reset_model (random_humanoid.py:219-234) exactly as humanoid_reset_kernel does it -- the same
   // Philox streams and draw order (q 0..23, then v 0..22), set_state -> sim.forward() with the masses in force, THEN
-  // set_random_task -- with the forward's kinematics / com / velocities over the pair's local trees.
+  // set_random_task -- as humanoid_pair.hpp's reset_lane over the pair's local trees.
   if (fused_reset && d) {
     const unsigned ep = s.episode[i] + 1;
     rocrand_state_philox4x32_10 st;
     rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
-    static_for<0, hum::NQ>([&](auto KK) { constexpr int k = KK;
-      const float val = c_hum.qpos0[k] + 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-      if constexpr (k < 10) ql[k] = val;                              // free joint + the three abdomen hinges: replicated
-      else static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD;
-        if constexpr (pr::gdR(ld) + 1 == k) ql[ld + 1] = left ? ql[ld + 1] : val;
-        if constexpr (pr::gdL(ld) + 1 == k) ql[ld + 1] = left ? val : ql[ld + 1]; }); });
-    static_for<0, hum::NV>([&](auto KK) { constexpr int k = KK;
-      const float val = 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
-      if constexpr (k < 9) vl[k] = val;
-      else static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD;
-        if constexpr (pr::gdR(ld) == k) vl[ld] = left ? vl[ld] : val;
-        if constexpr (pr::gdL(ld) == k) vl[ld] = left ? val : vl[ld]; }); });
-    {
-      pr::PSmooth<float> S;
-      pr::kinematics(p, c_hum, ql, S);
-      pr::com_pos(p, c_hum, L, S);
-      float qb[pr::LD];
-      pr::com_vel_rne(p, c_hum, vl, S, qb);
-      static_for<0, pr::LB>([&](auto BB) { constexpr int b = BB; for (int k = 0; k < 10; k++) park.cinert[b][k] = S.cinert[b][k]; for (int k = 0; k < 6; k++) park.cvel[b][k] = S.cvel[b][k]; xp[b] = S.xipos[b][0]; });
-      static_for<0, pr::LD>([&](auto II) { park.act[II] = 0.0f; });     // sim.reset() zeroes data.ctrl
-    }
-    if (fl.noisy) {
-      rocrand_state_philox4x32_10 st2;
-      rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
-      for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st2);
-    }
-    pr::emit_obs(p, ql, vl, park, [&](auto RR, auto RL, float val) {
-      constexpr int rr = RR, rl = RL;
-      if constexpr (rr < 45 && rl < 45) { if (fl.noisy) val += left ? nz[rl] : nz[rr]; }
-      (obs + (left ? (size_t)rl : (size_t)rr) * B)[i] = val;
-    });
-    static_for<9, pr::LD>([&](auto DD) { constexpr int ld = DD; const size_t g = left ? pr::gdL(ld) : pr::gdR(ld);
-      (s.qpos + (g + 1) * B)[i] = ql[ld + 1]; (s.qvel + g * B)[i] = vl[ld]; });
-    static_for<3, pr::LB>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(left ? pr::gbL(lb) : pr::gbR(lb)) * B)[i] = xp[lb]; });
+    pr::reset_lane(p, c_hum, L, [&]() { return rocrand_uniform(&st); }, ql, vl, xp, park);
+    if (fl.noisy) hum_obs_noise(s, fl, i, (unsigned long long)ep * EP_STRIDE + STEP_BASE, nz);
+    put_obs(obs, nullptr);
+    pr::store_lane(left, wr, ql, vl, xp);
     if (!left) {
       s.episode[i] = ep;
-      static_for<0, 10>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[i] = ql[k]; });
-      static_for<0, 9>([&](auto KK) { constexpr int k = KK; (s.qvel + (size_t)k * B)[i] = vl[k]; });
-      static_for<0, 3>([&](auto BB) { constexpr int lb = BB; (s.aux + (size_t)(lb + 1) * B)[i] = xp[lb]; });
       s.t[i] = 0; s.done[i] = 0;
       if (resample && dr.type != REX_DR_NONE)
         sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, B, i, s.counters);

@@ -2,7 +2,8 @@
 //
 // The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
-// math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp, the post-passes vecnorm.hpp and rollout.hpp.  Profiling probes
+// math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp (the last also owns the pair kernel's view of the SoA state: load_lane /
+// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp and rollout.hpp.  Profiling probes
 // live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.

@@ -337,3 +337,62 @@ def test_one_lane_step_kernel_matches_the_oracle(torch_mod):
         assert_lanes_explained(np.abs(o - ref["obs"]).max(1) / os_, sens["obs"] / os_, TOL_OBS, CAP_OBS, label="humanoid REX_HUM_PAIR=%d |dobs|rel" % pair)
         assert_lanes_explained(np.abs(r - ref["reward"]), sens["reward"], TOL_REW, CAP_REW, label="humanoid REX_HUM_PAIR=%d |dreward|" % pair)
     assert_lanes_explained(np.abs(outs[0][0] - outs[1][0]).max(1) / os_, sens["obs"] / os_, TOL_OBS, CAP_OBS, label="one-lane vs pair kernel |dobs|rel")
+
+
+@pytest.mark.parametrize("B", [33, 1])
+def test_forced_time_limit_reset_fused_vs_separate(torch_mod, B):
+    """One step with t = max_episode_steps - 1 in the odd lanes (lane 0 of the lone pair): those lanes are truncated and restart -- inside
+    the step launch (humanoid_pair_step_kernel's reset_lane / store_lane) or by the masked humanoid_reset_kernel launch -- while their
+    neighbours take an ordinary step.  B = 33: one full block of 32 envs and a second block holding a single pair.  Forced lanes against
+    reset_model of the oracle with the masses of the episode that ended, the others against its step; the two reset paths use the same
+    Philox streams, draw order and expression, so their states agree bit for bit."""
+    import random_envs_amd as rex
+    from oracle_bindings import oracle_humanoid_reset_obs, oracle_humanoid_step, oracle_sensitivity
+    from parity_util import assert_lanes_explained, create_knobs
+    torch = torch_mod
+    f64 = lambda x: x.cpu().numpy().astype(np.float64)
+    forced = np.zeros(B, bool)
+    forced[1::2] = True
+    if B == 1:
+        forced[0] = True
+    a = np.random.RandomState(31).uniform(-.4, .4, (B, 17)).astype(np.float32)
+    end = {}
+    for fused in (1, 0):
+        with create_knobs(REX_HUM_FUSED_RESET=fused):
+            env = rex.make("RandomHumanoid-v0", batch=B, seed=29)
+        lo, hi = env.get_task_search_bounds()
+        env.set_dr_distribution("uniform", np.stack([lo, hi], 1).ravel().tolist()); env.set_dr_training(True)
+        env.reset()
+        st = env.get_full_state()
+        st["t"][torch.as_tensor(forced)] = env.max_episode_steps - 1
+        env.set_full_state(st)
+        q0, v0, xi_before, aux0 = f64(st["qpos"]), f64(st["qvel"]), f64(st["task"]), f64(st["aux"].t())
+        obs, r, d, info = env.step(torch.as_tensor(a))
+        obs, r, d, trunc = f64(obs), f64(r), d.cpu().numpy(), info["TimeLimit.truncated"].cpu().numpy()
+        now = env.get_full_state()
+        q1, v1, xi_after = f64(now["qpos"]), f64(now["qvel"]), f64(now["task"])
+        tag = "humanoid B=%d fused=%d" % (B, fused)
+        # forced lanes: truncated, restarted, the observation is reset_model's with the OLD masses, the task redrawn afterwards
+        assert d[forced].all() and trunc[forced].all() and (now["t"].cpu().numpy()[forced] == 0).all(), tag
+        ref, xip = oracle_humanoid_reset_obs(q1[forced], v1[forced], xi_before[forced])
+        e = np.abs(obs[forced] - ref).max(1) / (1 + np.abs(ref).max(1))
+        ex = np.abs(f64(now["aux"].t())[forced] - xip).max()
+        print("%s: forced lanes obs rel %.2e, xipos %.2e" % (tag, e.max(), ex))
+        assert e.max() < 2e-5 and ex < 1e-5, (tag, e.max(), ex)
+        assert np.abs(xi_after[forced] - xi_before[forced]).max(1).min() > 1e-3, tag
+        # the other lanes: an ordinary step, their task untouched
+        keep = ~forced
+        assert np.array_equal(xi_after[keep], xi_before[keep]), tag
+        if keep.any():
+            assert not d[keep].any() and not trunc[keep].any() and (now["t"].cpu().numpy()[keep] == 1).all(), tag
+            ins = [q0[keep], v0[keep], a[keep].astype(np.float64), xi_before[keep]]
+            ref, sens = oracle_sensitivity(lambda q_, v_, a_, x_: oracle_humanoid_step(q_, v_, a_, x_, xipos_x_prev=aux0[keep]), ins,
+                                           ["obs", "reward"], trials=2)
+            os_ = 1 + np.abs(ref["obs"]).max(1)
+            assert_lanes_explained(np.abs(obs[keep] - ref["obs"]).max(1) / os_, sens["obs"] / os_, TOL_OBS, CAP_OBS, label=tag + " |dobs|rel")
+            assert_lanes_explained(np.abs(r[keep] - ref["reward"]), sens["reward"], TOL_REW, CAP_REW, label=tag + " |dreward|")
+        c = env.counters(); assert c["nonfinite"] == 0 and c["overflow"] == 0, (tag, c)
+        end[fused] = [now[k].cpu().numpy() for k in ("qpos", "qvel", "task")]
+        env.close()
+    for x, y, name in zip(end[1], end[0], ("qpos", "qvel", "xi")):
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), "B=%d: %s differs between the fused and the separate reset" % (B, name)

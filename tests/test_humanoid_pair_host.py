@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from oracle_bindings import _p, oracle_humanoid_step
+from oracle_bindings import _p, oracle_humanoid_reset_obs, oracle_humanoid_step
 from random_envs_amd.specs import SPECS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,3 +87,75 @@ def test_pile_ups_all_solver_paths(hp):
     assert (out["nrows"] > 21).sum() >= 3 and (out["nrows"] <= 16).sum() >= 1, np.sort(out["nrows"])
     assert ev[ok].max() < 1e-7, ev[ok].max()
 
+
+
+# humanoid.xml's own orders, written out independently of the code under test: bodies 1 torso, 2 lwaist, 3 pelvis, 4-6 right thigh / shin /
+# foot, 7-9 left, 10-11 right upper / lower arm, 12-13 left; dofs 0-5 root, 6-8 abdomen z / y / x, 9-12 right hip x / z / y + knee, 13-16
+# left, 17-19 right shoulder 1 / 2 + elbow, 20-22 left; motors (:106-122) abdomen y, z, x, right leg, left leg, right arm, left arm
+BODY = ([1, 2, 3, 4, 5, 6, 10, 11], [1, 2, 3, 7, 8, 9, 12, 13])
+DOF = (list(range(9)) + [9, 10, 11, 12, 17, 18, 19], list(range(9)) + [13, 14, 15, 16, 20, 21, 22])
+MOTOR = ([1, 0, 2, 3, 4, 5, 6, 11, 12, 13], [1, 0, 2, 7, 8, 9, 10, 14, 15, 16])
+QPOS0 = np.array([0, 0, 1.4, 1, 0, 0, 0] + [0] * 17, dtype=float)
+
+
+def test_load_store_round_trip(hp):
+    """load_lane then store_lane with nothing between (the kernel's own layout code): every state row comes back where it was, from
+    exactly one lane; every xi and action row reaches the lane(s) that use it."""
+    n = 3
+    rows = dict(qpos=24, qvel=23, act=17, xi=30, aux=14)
+    src = {}
+    for j, (k, r) in enumerate(rows.items()):
+        src[k] = 1000.0 * (j + 1) + np.arange(r * n, dtype=float).reshape(r, n)     # distinct over all blocks, rows and envs
+    out = {k: np.full((rows[k], n), np.nan) for k in ("qpos", "qvel", "aux")}
+    lane = np.full((2, 34, n), np.nan)
+    hp.hp_roundtrip(n, _p(src["qpos"]), _p(src["qvel"]), _p(src["act"]), _p(src["xi"]), _p(src["aux"]),
+                    _p(out["qpos"]), _p(out["qvel"]), _p(out["aux"]), _p(lane))
+    assert np.array_equal(out["qpos"], src["qpos"]) and np.array_equal(out["qvel"], src["qvel"])
+    assert np.array_equal(out["aux"][1:], src["aux"][1:]) and np.all(out["aux"][0] == 0)
+    assert not any(np.isnan(o).any() for o in out.values()) and not np.isnan(lane).any()
+    used = set()
+    for s in (0, 1):
+        assert np.array_equal(lane[s, :8], src["xi"][[b - 1 for b in BODY[s]]])                     # body_mass[1:] = xi[:13]
+        assert np.all(lane[s, 8:14] == 0) and np.array_equal(lane[s, 14:24], src["xi"][[13 + d - 6 for d in DOF[s][6:]]])
+        assert np.array_equal(lane[s, 24:], src["act"][MOTOR[s]])
+        used |= set(MOTOR[s])
+    assert used == set(range(17))                                                                   # each of the 17 action rows is consumed
+
+
+@pytest.fixture(scope="module")
+def reset64(hp):
+    """hp_reset (reset_lane + emit_obs + store_lane, the kernel's fused auto-reset) at n = 64 in both precisions, with its inputs"""
+    n = 64; rng = np.random.RandomState(7)
+    draws = rng.uniform(0, 1, (47, n)).astype(np.float32).astype(np.float64)        # (fp32-representable: both precisions see the same uniforms)
+    xi = np.array(SPECS["humanoid"].nominal_task) * rng.uniform(.8, 1.2, (n, 30))
+    xs = np.ascontiguousarray(xi.T)
+    res = {}
+    for f32 in (0, 1):
+        qo = np.full((24, n), np.nan); vo = np.full((23, n), np.nan); obs = np.full((376, n), np.nan); xo = np.full((14, n), np.nan)
+        hp.hp_reset(f32, n, _p(draws), _p(xs), _p(qo), _p(vo), _p(obs), _p(xo))
+        res[f32] = dict(qpos=qo.T.copy(), qvel=vo.T.copy(), obs=obs.T.copy(), xipos_x=xo.T.copy())
+    return dict(draws=draws, xi=xi, out=res)
+
+
+def test_reset_vs_oracle(reset64):
+    draws, xi = reset64["draws"], reset64["xi"]
+    q = (QPOS0[:, None] + 0.01 * (2 * (1 - draws[:24]) - 1)).T                       # random_humanoid.py:220-229, NQ draws then NV
+    v = (0.01 * (2 * (1 - draws[24:]) - 1)).T
+    for f32, tq, to, tx in ((0, 0.0, 1e-10, 1e-12), (1, 1.2e-7, 2e-5, 1e-5)):
+        out = reset64["out"][f32]
+        eq = max(np.abs(out["qpos"] - q).max(), np.abs(out["qvel"] - v).max())
+        ref, xip = oracle_humanoid_reset_obs(out["qpos"], out["qvel"], xi)
+        eo = (np.abs(out["obs"] - ref).max(1) / (1 + np.abs(ref).max(1))).max()
+        ex = np.abs(out["xipos_x"] - xip).max()
+        print("hp_reset f32=%d: |dq| %.2e, obs rel %.2e, xipos %.2e" % (f32, eq, eo, ex))
+        assert eq <= tq and eo < to and ex < tx, (f32, eq, eo, ex)
+
+
+def test_reset_then_step(hp, reset64):
+    """the reset leaves the xipos that the next mass_center() reads"""
+    out, xi = reset64["out"][0], reset64["xi"]
+    a = np.random.RandomState(8).uniform(-.4, .4, (64, 17))
+    _, xip = oracle_humanoid_reset_obs(out["qpos"], out["qvel"], xi)
+    ref = oracle_humanoid_step(out["qpos"], out["qvel"], a, xi, xipos_x_prev=xip)
+    got = _step(hp, 0, out["qpos"], out["qvel"], a, xi, xprev=out["xipos_x"])
+    assert np.abs(got["reward"] - ref["reward"]).max() < 1e-8
