@@ -376,6 +376,60 @@ int rex_eplog_read(rex_t* h, int64_t* out, int clear);
 int rex_eplog_get_lane_state(rex_t* h, double* ep_return, int32_t* ep_len, float* shadow_task, void* stream);
 int rex_eplog_set_lane_state(rex_t* h, const double* ep_return, const int32_t* ep_len, const float* shadow_task, void* stream);
 
+/* ---- off-policy replay buffer: fused store of a transition per env, on-device sampling -----------------------------------------
+ * The layer above step() in every off-policy loop (SAC / TD3 / DDPG, and every domain-randomisation loop that reuses data across
+ * distribution updates): stable-baselines3's ReplayBuffer (common/buffers.py: add, sample, _get_samples) and
+ * OffPolicyAlgorithm._store_transition (common/off_policy_algorithm.py).  No reference counterpart of its own.  rex_step, rex_norm_*,
+ * rex_rollout_* and rex_eplog_* are untouched.  The names say "rbuf": rex_replay is something else -- the offline replay of LOGGED
+ * transitions under candidate xi -- and shares nothing with these calls.
+ *
+ * Storage belongs to the caller: a ring of T time slots over the handle's batch B in device memory, TRANSITION-MAJOR (a buffer is
+ * written once per transition and read at random many times; a whole transition is one contiguous row).  Transition id s = t * B + b:
+ *   obs, next_obs [T][B][obs_dim] f32, action [T][B][act_dim] 4-byte words (copied bit for bit: float, or the cart-pole's int32),
+ *   reward [T][B] f32, done / timeout [T][B] uint8.
+ * The handle contributes the device, the dims and B, and holds no buffer state: slot, fill level, seed and draw number are arguments,
+ * as in rex_rollout_*.  rex_rbuf_enable makes the only allocation (the bad-index counter; it synchronises); every other rex_rbuf_* call
+ * before it returns REX_ERR_STATE.  The launching calls neither allocate nor synchronise. */
+typedef struct rex_rbuf_buffers {
+  float* obs;
+  float* next_obs;
+  void* action;
+  float* reward;
+  uint8_t* done;
+  uint8_t* timeout;
+  int64_t T;
+} rex_rbuf_buffers;
+int rex_rbuf_enable(rex_t* h);
+/* ReplayBuffer.add, ONE launch: the SoA buffers rex_step reads and writes -- obs [obs_dim][B] (the observation the action was computed
+ * from), action [act_dim][B], reward [B], done [B], next_obs [obs_dim][B] (what rex_step returned, i.e. after the auto-reset), and
+ * optionally terminal_obs [obs_dim][B] and truncated [B] -- are transposed into slot t.  For lane b, s = t * B + b:
+ *   obs[s][:] = obs[:, b];  action[s][:] = action[:, b];  reward[s] = reward[b];  done[s] = done[b] != 0;
+ *   next_obs[s][:] = (terminal_obs && done[b]) ? terminal_obs[:, b] : next_obs[:, b];  timeout[s] = truncated ? truncated[b] != 0 : 0.
+ * A pure copy.  t outside [0, T): REX_ERR_ARG. */
+int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, const float* obs, const void* action, const float* reward,
+                 const uint8_t* done, const float* next_obs, const float* terminal_obs, const uint8_t* truncated, void* stream);
+/* ReplayBuffer.sample, ONE launch, no host-side randomness: `size` is the number of valid slots (1 <= size <= T, else REX_ERR_ARG),
+ * N = size * B.  Sample j (0-based) evaluates Philox4x32-10 with key (lo32(seed), hi32(seed)) and counter (lo32(j), hi32(j), lo32(draw),
+ * hi32(draw)), takes u = w0 | (w1 << 32), and its id is the high 64 bits of the 128-bit product u * N (bias at most N / 2^64); draws are
+ * with replacement and depend on (seed, draw, size, B, j) only.
+ * The outputs use the learner's layout and are each optional (NULL skips): obs_out, next_obs_out [n][obs_dim] and action_out
+ * [n][act_dim] ROW-MAJOR, reward_out [n] f32, done_out [n] f32 = (done && !timeout) ? 1 : 0 (SB3's dones * (1 - timeouts): a time-limit
+ * end still bootstraps), index_out [n] int64 the ids used.
+ * normalise != 0 is SB3's sample(batch_size, env=vec_normalize) and needs rex_norm_enable on the handle (else REX_ERR_STATE): the stored
+ * values stay raw; the kernel reads the running statistics from device memory as they stand when it runs (stream-ordered behind the last
+ * rex_norm_step).  With norm_obs on, obs_out and next_obs_out are clip((x - mean) / sqrt(var + epsilon), +-clip_obs) of their row's
+ * statistic; with norm_reward on, reward_out is clip(r / sqrt(var_ret + epsilon), +-clip_reward) -- the arithmetic of rex_norm_step, so
+ * under frozen statistics the bits equal what rex_norm_step returns for those values.  A switch that is off leaves its output raw. */
+int rex_rbuf_sample(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t n, uint64_t seed, uint64_t draw, int normalise,
+                    float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out, int64_t* index_out,
+                    void* stream);
+/* The same launch with the caller's ids: index [dev, int64 n] (prioritised schemes, tests).  An id outside [0, T * B) is never
+ * dereferenced: that sample's outputs are zeros and a device counter is incremented (rex_rbuf_read_bad_indices). */
+int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int normalise, float* obs_out,
+                    float* next_obs_out, void* action_out, float* reward_out, float* done_out, void* stream);
+/* out [host, 1 int64]: out-of-range ids rex_rbuf_gather met since the last clearing read.  Synchronises. */
+int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

@@ -22,6 +22,7 @@ SYMBOLS = [
     "rex_rollout_enable", "rex_rollout_add", "rex_rollout_gae", "rex_rollout_adv_stats", "rex_rollout_get_adv_stats", "rex_rollout_gather",
     "rex_rollout_read_bad_indices",
     "rex_eplog_enable", "rex_eplog_step", "rex_eplog_sync", "rex_eplog_read", "rex_eplog_get_lane_state", "rex_eplog_set_lane_state",
+    "rex_rbuf_enable", "rex_rbuf_add", "rex_rbuf_sample", "rex_rbuf_gather", "rex_rbuf_read_bad_indices",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -47,6 +48,10 @@ class RexRolloutBuffers(ctypes.Structure):
 
 class RexEplogBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("task", "ep_return", "ep_len", "flags", "env", "step")] + [("capacity", ctypes.c_int64)]
+
+
+class RexRbufBuffers(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "next_obs", "action", "reward", "done", "timeout")] + [("T", ctypes.c_int64)]
 
 
 class RexError(RuntimeError):
@@ -124,6 +129,12 @@ def lib():
     L.rex_eplog_read.argtypes = [vp, ctypes.POINTER(i64), i32]
     L.rex_eplog_get_lane_state.argtypes = [vp, vp, vp, vp, vp]
     L.rex_eplog_set_lane_state.argtypes = [vp, vp, vp, vp, vp]
+    rp = ctypes.POINTER(RexRbufBuffers)
+    L.rex_rbuf_enable.argtypes = [vp]
+    L.rex_rbuf_add.argtypes = [vp, rp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rbuf_sample.argtypes = [vp, rp, i64, i64, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rbuf_gather.argtypes = [vp, rp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    L.rex_rbuf_read_bad_indices.argtypes = [vp, ctypes.POINTER(i64), i32]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

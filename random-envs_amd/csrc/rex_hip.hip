@@ -3,7 +3,7 @@
 // The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
 // math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp (the last also owns the pair kernel's view of the SoA state: load_lane /
-// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp and rollout.hpp.  Profiling probes
+// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp and replay_buffer.hpp.  Profiling probes
 // live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.
@@ -33,6 +33,7 @@
 #include "launch_shape.hpp"
 #include "vecnorm.hpp"
 #include "rollout.hpp"
+#include "replay_buffer.hpp"
 #include "eplog.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
@@ -130,6 +131,8 @@ struct rex_env {
   // task, one count per block -- and the launch parameters with the caller's table in them
   void* eplog_mem = nullptr;
   eplog::Params eplog{};
+  // rex_rbuf_* (replay_buffer.hpp): the bad-index counter rex_rbuf_enable allocates.  Nothing else of a replay buffer lives in the handle.
+  void* rbuf_mem = nullptr;
 };
 constexpr size_t EV_POOL = 8192;
 
@@ -447,6 +450,7 @@ extern "C" int rex_destroy(rex_t* h) {
   if (h->norm_mem) hipFree(h->norm_mem);
   if (h->rollout_mem) hipFree(h->rollout_mem);
   if (h->eplog_mem) hipFree(h->eplog_mem);
+  if (h->rbuf_mem) hipFree(h->rbuf_mem);
   for (auto e : h->ev0) hipEventDestroy(e);
   for (auto e : h->ev1) hipEventDestroy(e);
   delete h;
@@ -1235,5 +1239,106 @@ extern "C" int rex_eplog_set_lane_state(rex_t* h, const double* ep_return, const
   HIP_TRY(hipMemcpyAsync(h->eplog.lanes.ep_return, ep_return, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(h->eplog.lanes.ep_len, ep_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(h->eplog.lanes.shadow, shadow_task, sizeof(float) * B * (size_t)h->dims.task_dim, hipMemcpyDeviceToDevice, st));
+  return REX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// off-policy replay buffer (replay_buffer.hpp): fused transposing add and on-device sampling over caller-owned transition-major buffers
+// ------------------------------------------------------------------------------------------
+#define REX_RBUF_ON(h, fn) \
+  do { if (!(h)->rbuf_mem) return set_err(REX_ERR_STATE, fn ": rex_rbuf_enable has not been called on this handle"); } while (0)
+
+extern "C" int rex_rbuf_enable(rex_t* h) {
+  REX_ENTER(h, "rex_rbuf_enable");
+  if (!h->rbuf_mem) HIP_TRY(hipMalloc(&h->rbuf_mem, sizeof(unsigned long long)));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemset(h->rbuf_mem, 0, sizeof(unsigned long long)));
+  return REX_OK;
+}
+
+// the caller's struct with the handle's sizes; every buffer is required
+static int rbuf_buf(const rex_env* h, const rex_rbuf_buffers* b, const char* fn, rbuf::Buf* out) {
+  if (!b) return set_err(REX_ERR_ARG, "%s: null buffer description", fn);
+  if (!b->obs || !b->next_obs || !b->action || !b->reward || !b->done || !b->timeout)
+    return set_err(REX_ERR_ARG, "%s: every pointer of rex_rbuf_buffers is required", fn);
+  if (b->T <= 0) return set_err(REX_ERR_ARG, "%s: T must be > 0 (got %lld)", fn, (long long)b->T);
+  *out = rbuf::Buf{(uint32_t*)b->obs, (uint32_t*)b->next_obs, (uint32_t*)b->action, b->reward, b->done, b->timeout,
+                   (long long)b->T, h->B, h->dims.obs_dim, h->dims.act_dim};
+  return REX_OK;
+}
+
+extern "C" int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, const float* obs, const void* action, const float* reward,
+                            const uint8_t* done, const float* next_obs, const float* terminal_obs, const uint8_t* truncated, void* stream) {
+  REX_ENTER(h, "rex_rbuf_add");
+  REX_RBUF_ON(h, "rex_rbuf_add");
+  rbuf::AddParams p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_add", &p.buf)) return rc;
+  if (t < 0 || t >= buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_add: slot %lld outside [0, %lld)", (long long)t, (long long)buf->T);
+  if (!obs || !action || !reward || !done || !next_obs) return set_err(REX_ERR_ARG, "rex_rbuf_add: null input");
+  p.src = rbuf::AddSrc{(const uint32_t*)obs, (const uint32_t*)action, reward, done, (const uint32_t*)next_obs, (const uint32_t*)terminal_obs, truncated};
+  p.slot = t;
+  const long long tiles = rbuf::add_tiles(h->B);
+  if (tiles > 0x7fffffffLL) return set_err(REX_ERR_ARG, "rex_rbuf_add: batch %lld is more than one launch takes", h->B);
+  const unsigned groups = (unsigned)rbuf::add_groups(p.buf.obs_dim, p.buf.act_dim);
+  hipLaunchKernelGGL(rbuf::rb_add_kernel, dim3((unsigned)tiles, groups), dim3(rbuf::BLOCK), 0, (hipStream_t)stream, p);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+// the one launch behind rex_rbuf_sample (index == nullptr: the ids are drawn) and rex_rbuf_gather
+static int launch_rbuf_sample(const rex_env* h, const char* fn, rbuf::SampleParams p, int normalise, hipStream_t st) {
+  if (normalise) {
+    if (!h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
+    const rex_norm_config& c = h->norm_cfg;
+    p.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
+  }
+  if (p.n == 0) return REX_OK;
+  const long long blocks = rbuf::sample_blocks(p.n);
+  if (blocks > 0x7fffffffLL) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
+  // 16-byte accesses: with dim a multiple of 4 every row of a 16-byte aligned buffer starts 16-byte aligned
+  const rbuf::Buf& b = p.buf;
+  p.vec_obs = (b.obs_dim % 4 == 0 && aligned16(b.obs) && aligned16(b.next_obs) && aligned16(p.out.obs) && aligned16(p.out.next_obs)) ? 1 : 0;
+  p.vec_act = (b.act_dim % 4 == 0 && aligned16(b.action) && aligned16(p.out.action)) ? 1 : 0;
+  p.bad = (unsigned long long*)h->rbuf_mem;
+  hipLaunchKernelGGL(rbuf::rb_sample_kernel, dim3((unsigned)blocks), dim3(rbuf::BLOCK), 0, st, p);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_rbuf_sample(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t n, uint64_t seed, uint64_t draw, int normalise,
+                               float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out, int64_t* index_out,
+                               void* stream) {
+  REX_ENTER(h, "rex_rbuf_sample");
+  REX_RBUF_ON(h, "rex_rbuf_sample");
+  rbuf::SampleParams p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample", &p.buf)) return rc;
+  if (size < 1 || size > buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_sample: size %lld outside [1, %lld]", (long long)size, (long long)buf->T);
+  if (n < 0) return set_err(REX_ERR_ARG, "rex_rbuf_sample: n must be >= 0");
+  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, (long long*)index_out};
+  p.n = n; p.N = (long long)size * h->B; p.seed = seed; p.draw = draw;
+  return launch_rbuf_sample(h, "rex_rbuf_sample", p, normalise, (hipStream_t)stream);
+}
+
+extern "C" int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int normalise, float* obs_out,
+                               float* next_obs_out, void* action_out, float* reward_out, float* done_out, void* stream) {
+  REX_ENTER(h, "rex_rbuf_gather");
+  REX_RBUF_ON(h, "rex_rbuf_gather");
+  rbuf::SampleParams p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather", &p.buf)) return rc;
+  if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rbuf_gather: n must be >= 0 and index given");
+  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr};
+  p.index = (const long long*)index; p.n = n; p.N = p.buf.T * p.buf.B;
+  return launch_rbuf_sample(h, "rex_rbuf_gather", p, normalise, (hipStream_t)stream);
+}
+
+extern "C" int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear) {
+  REX_ENTER(h, "rex_rbuf_read_bad_indices");
+  REX_RBUF_ON(h, "rex_rbuf_read_bad_indices");
+  if (!out) return set_err(REX_ERR_ARG, "rex_rbuf_read_bad_indices: null argument");
+  unsigned long long v = 0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&v, h->rbuf_mem, sizeof v, hipMemcpyDeviceToHost));
+  *out = (int64_t)v;
+  if (clear) HIP_TRY(hipMemset(h->rbuf_mem, 0, sizeof v));
   return REX_OK;
 }

@@ -1,0 +1,156 @@
+"""ReplayBuffer: the off-policy replay buffer on the device.
+
+The layer every off-policy loop (SAC, TD3, DDPG, and every domain-randomisation loop that reuses data across distribution
+updates) places above ``step()`` -- stable-baselines3's ``ReplayBuffer`` -- over tensors this object owns.  Storage is a ring
+of ``n_slots`` time slots over the env's batch, TRANSITION-MAJOR (``obs`` / ``next_obs [T, B, obs_dim]``, ``action
+[T, B, act_dim]``, ``reward`` / ``done`` / ``timeout [T, B]``): one HIP launch transposes a step out of the SoA buffers
+``step_soa_full`` returns (terminal observations go into ``next_obs`` on the finished lanes), one launch draws the ids of a
+minibatch on the device (Philox4x32-10, no host randomness, no synchronisation) and copies the whole rows into the row-major
+``[n, dim]`` layout a network reads, normalised with the running statistics of a ``NormalizedVecRandomEnv`` on request
+(``rex_rbuf_*`` of include/rex.h, csrc/replay_buffer.hpp).
+"""
+import ctypes
+
+from . import _native
+
+_FIELDS = ("obs", "next_obs", "action", "reward", "done", "timeout")
+
+
+class ReplayBuffer:
+    """``ReplayBuffer(env, n_slots, seed=0)`` over a :class:`VecRandomEnv` or a :class:`NormalizedVecRandomEnv`; it holds
+    ``n_slots * env.batch`` transitions."""
+
+    def __init__(self, env, n_slots, seed=0):
+        import torch
+        self._torch = torch
+        self.env = env
+        base = getattr(env, "env", env)            # the wrapped env of a NormalizedVecRandomEnv
+        self._base = base
+        self._normalized = base is not env
+        self._L, self._h = base._L, base._h
+        self.n_slots, self.seed = int(n_slots), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if self.n_slots <= 0:
+            raise ValueError("ReplayBuffer: n_slots must be > 0")
+        self.batch, self.device = base.batch, base.device
+        self.obs_dim, self.act_dim = int(base.dims.obs_dim), int(base.dims.act_dim)
+        _native.check(self._L.rex_rbuf_enable(self._h))
+        T, B = self.n_slots, self.batch
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.obs, self.next_obs = torch.zeros(T, B, self.obs_dim, **f32), torch.zeros(T, B, self.obs_dim, **f32)
+        self.action = torch.zeros(T, B, self.act_dim, dtype=torch.int32 if base.dims.discrete_action else torch.float32, device=self.device)
+        self.reward = torch.zeros(T, B, **f32)
+        self.done, self.timeout = torch.zeros(T, B, dtype=torch.uint8, device=self.device), torch.zeros(T, B, dtype=torch.uint8, device=self.device)
+        self._desc = _native.RexRbufBuffers(*[getattr(self, k).data_ptr() for k in _FIELDS], T)
+        self.pos, self.full, self.draws = 0, False, 0
+
+    # ------------------------------------------------------------------ plumbing
+    @staticmethod
+    def _p(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def _stream(self):
+        return self._base._stream()
+
+    def _check(self, t, shape, dtypes, name):
+        if t.device != self.device or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous():
+            raise ValueError("ReplayBuffer: %s must be a contiguous %s tensor of %s on %s" % (name, list(shape), dtypes[0], self.device))
+
+    def _normalise_flag(self, normalize):
+        return int(self._normalized if normalize is None else bool(normalize))
+
+    def __len__(self):
+        """Transitions stored."""
+        return (self.n_slots if self.full else self.pos) * self.batch
+
+    # ------------------------------------------------------------------ collect
+    def add(self, obs_soa, action_soa, reward, done, next_obs_soa, terminal_obs_soa=None, truncated=None):
+        """Store one transition per env in ONE launch: ``obs_soa`` [obs_dim, B] (the observation the action was computed
+        from), ``action_soa`` [act_dim, B], ``reward`` [B] float32, ``done`` [B] uint8 or bool, ``next_obs_soa`` [obs_dim, B]
+        (what the step returned, i.e. after the auto-reset).  With ``terminal_obs_soa`` [obs_dim, B] the finished lanes store
+        it as their ``next_obs``; with ``truncated`` [B] the time-limit ends are kept apart, so ``sample`` returns ``done = 0``
+        for them.  Store RAW values when sampling with ``normalize``.  The inputs are read on the env's stream: keep them
+        unchanged until that work has run, as with ``step_soa``."""
+        t = self._torch
+        B, byte = self.batch, (t.uint8, t.bool)
+        self._check(obs_soa, (self.obs_dim, B), (t.float32,), "obs_soa")
+        self._check(action_soa, (self.act_dim, B), (self.action.dtype,), "action_soa")
+        self._check(reward, (B,), (t.float32,), "reward")
+        self._check(done, (B,), byte, "done")
+        self._check(next_obs_soa, (self.obs_dim, B), (t.float32,), "next_obs_soa")
+        if terminal_obs_soa is not None:
+            self._check(terminal_obs_soa, (self.obs_dim, B), (t.float32,), "terminal_obs_soa")
+        if truncated is not None:
+            self._check(truncated, (B,), byte, "truncated")
+        _native.check(self._L.rex_rbuf_add(self._h, ctypes.byref(self._desc), self.pos, self._p(obs_soa), self._p(action_soa), self._p(reward),
+                                           self._p(done), self._p(next_obs_soa), self._p(terminal_obs_soa), self._p(truncated), self._stream()))
+        self.pos += 1
+        if self.pos == self.n_slots:
+            self.pos, self.full = 0, True
+
+    # ------------------------------------------------------------------ learn
+    def _outputs(self, n, with_index):
+        t = self._torch
+        f32 = dict(dtype=t.float32, device=self.device)
+        out = dict(obs=t.empty(n, self.obs_dim, **f32), next_obs=t.empty(n, self.obs_dim, **f32),
+                   action=t.empty(n, self.act_dim, dtype=self.action.dtype, device=self.device), reward=t.empty(n, **f32), done=t.empty(n, **f32))
+        if with_index:
+            out["index"] = t.empty(n, dtype=t.int64, device=self.device)
+        return out
+
+    def sample(self, batch_size, normalize=None):
+        """One minibatch of ``batch_size`` transitions drawn uniformly with replacement from those stored, in ONE launch and
+        without a synchronisation: a dict of ``obs`` / ``next_obs`` [n, obs_dim], ``action`` [n, act_dim] (row-major),
+        ``reward`` [n], ``done`` [n] float32 (``done and not timeout``) and ``index`` [n] int64 (``s = t * B + b``).  The ids are
+        a function of (seed, number of the draw, fill level, batch, j).  ``normalize=None`` means "yes iff the env is a
+        ``NormalizedVecRandomEnv``": observations and rewards then come back normalised with its running statistics as
+        they stand."""
+        size = self.n_slots if self.full else self.pos
+        if size == 0:
+            raise RuntimeError("ReplayBuffer.sample: the buffer is empty")
+        n = int(batch_size)
+        out = self._outputs(n, True)
+        _native.check(self._L.rex_rbuf_sample(self._h, ctypes.byref(self._desc), size, n, self.seed, self.draws, self._normalise_flag(normalize),
+                                              self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]),
+                                              self._p(out["done"]), self._p(out["index"]), self._stream()))
+        self.draws += 1
+        return out
+
+    def gather(self, index, normalize=None):
+        """The same launch for the caller's ids ``index`` (int64 on the device): prioritised schemes, tests.  An id outside
+        ``[0, n_slots * batch)`` gives zeros and is counted (:meth:`bad_indices`)."""
+        t = self._torch
+        if index.device != self.device or index.dtype != t.int64 or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError("ReplayBuffer.gather: index must be a contiguous 1-d int64 tensor on %s" % self.device)
+        n = index.numel()
+        out = self._outputs(n, False)
+        _native.check(self._L.rex_rbuf_gather(self._h, ctypes.byref(self._desc), self._p(index), n, self._normalise_flag(normalize),
+                                              self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]),
+                                              self._p(out["done"]), self._stream()))
+        out["index"] = index
+        return out
+
+    def bad_indices(self, clear=True):
+        """Ids out of range the gathers met since the last clearing read (their outputs are zeros).  Synchronises."""
+        out = ctypes.c_int64()
+        _native.check(self._L.rex_rbuf_read_bad_indices(self._h, ctypes.byref(out), int(bool(clear))))
+        return int(out.value)
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self):
+        """Everything a resume needs: ``pos``, ``full``, ``seed``, ``draws`` and clones of the stored tensors.  A buffer restored
+        from it continues the same sample stream."""
+        d = dict(pos=self.pos, full=self.full, seed=self.seed, draws=self.draws)
+        d.update({k: getattr(self, k).clone() for k in _FIELDS})
+        return d
+
+    def load_state_dict(self, state):
+        for k in _FIELDS:
+            src = self._torch.as_tensor(state[k])
+            if tuple(src.shape) != tuple(getattr(self, k).shape):
+                raise ValueError("ReplayBuffer.load_state_dict: %s has shape %s, expected %s" % (k, list(src.shape), list(getattr(self, k).shape)))
+            getattr(self, k).copy_(src)
+        self.pos, self.full, self.seed, self.draws = int(state["pos"]), bool(state["full"]), int(state["seed"]), int(state["draws"])
+
+    def views(self):
+        """The stored tensors (zero-copy): ``obs`` / ``next_obs`` [T, B, obs_dim], ``action`` [T, B, act_dim], the rest [T, B]."""
+        return {k: getattr(self, k) for k in _FIELDS}

@@ -403,6 +403,16 @@ class VecRandomEnv(DRConfig):
             ctypes.c_void_p(self._reward.data_ptr()), ctypes.c_void_p(self._done.data_ptr()), None, None, self._stream()))
         return self._obs, self._reward, self._done
 
+    def step_soa_full(self, action_soa):
+        """``step_soa`` with the ``truncated`` and ``terminal_obs`` buffers passed as well (what an off-policy replay buffer
+        stores): returns the SoA obs / reward / done / truncated / terminal_obs buffers.  ``terminal_obs`` is meaningful on
+        the lanes with ``done`` set."""
+        _native.check(self._L.rex_step(
+            self._h, ctypes.c_void_p(action_soa.data_ptr()), ctypes.c_void_p(self._obs.data_ptr()),
+            ctypes.c_void_p(self._reward.data_ptr()), ctypes.c_void_p(self._done.data_ptr()),
+            ctypes.c_void_p(self._trunc.data_ptr()), ctypes.c_void_p(self._term_obs.data_ptr()), self._stream()))
+        return self._obs, self._reward, self._done, self._trunc, self._term_obs
+
     def step_count(self):
         return int(self._L.rex_step_count(self._h))
 
