@@ -583,16 +583,18 @@ struct CorrPlan {
   REX_HD CorrPlan(unsigned t_lim_, unsigned tm, int corr, bool base) : t_lim(t_lim_), even(SPLIT ? (tm & 0x55555555u) : tm), odd(SPLIT ? (tm & 0xAAAAAAAAu) : 0u) {
     nl = __builtin_popcount(t_lim);
     const int ne = __builtin_popcount(even), no = __builtin_popcount(odd), ng = nl + ne + no;
-    two = SPLIT && corr >= 2 && base && ng == 2 && ne <= 1 && no <= 1;
-    can = two || (base && corr != 0 && ng == 1);
+    // (`&` / `|` on 0 / 1 and value selects below, not `&&` / `||` / early returns: `corr` is wave-uniform, and a short circuit on it is a scalar branch)
+    two = SPLIT && bool(int(corr >= 2) & int(base) & int(ng == 2) & int(ne <= 1) & int(no <= 1));
+    can = bool(int(two) | (int(base) & int(corr != 0) & int(ng == 1)));
   }
-  REX_HD unsigned my_slots(unsigned vp) const { return !can ? 0u : (SPLIT ? (vp ? odd : even) : even); }
+  REX_HD unsigned my_slots(unsigned vp) const { const unsigned mine = SPLIT ? (vp ? odd : even) : even; return can ? mine : 0u; }
   REX_HD unsigned my_lim(unsigned vp) const {
-    if (!can) return 0u;
-    if constexpr (!SPLIT) return t_lim;
+    if constexpr (!SPLIT) return can ? t_lim : 0u;
     const unsigned lane_for_one = (even != 0u && odd == 0u) ? 1u : 0u;          // a single limit: the lane without a slot (lane 0 if neither has one)
     const unsigned lo = t_lim & (0u - t_lim), hi = t_lim & (t_lim - 1u);        // two limits: the lower one to lane 0
-    return nl == 1 ? (vp == lane_for_one ? t_lim : 0u) : (vp ? hi : lo);        // (nl == 0: lo = hi = 0)
+    const unsigned one = vp == lane_for_one ? t_lim : 0u, of_two = vp ? hi : lo;
+    const unsigned mine = nl == 1 ? one : of_two;                               // (nl == 0: lo = hi = 0)
+    return can ? mine : 0u;
   }
 };
 // z of MY group in the coupled system  [I + Cm Gmm, Cm X; Ct X^T, I + Ct Gtt] [zm; zt] = [wm; wt]  (X = Um^T Vt): eliminate the partner's block
@@ -659,7 +661,10 @@ REX_HD bool corr_step(const T (&H)[S::NV][S::NV], bool two, bool use, unsigned p
       const T idet = good ? rcp_t(det) : T(0);
       zt = (a22 * g[0].wt - a12 * g[0].wn) * idet; zn = (a11 * g[0].wn - a21 * g[0].wt) * idet;
     }
-    good = use && good && (pair_xchg(good ? 1u : 0u) != 0u);
+    // (the exchange outside the `&&`: a cross-lane read cannot be speculated, so a short circuit around it is a divergent branch -- save exec,
+    // skip, restore -- in the middle of the correction block)
+    const bool partner_good = pair_xchg(good ? 1u : 0u) != 0u;
+    good = use && good && partner_good;
     zt = good ? zt : T(0); zn = good ? zn : T(0);
     static_for<0, S::NV>([&](auto II) { constexpr int i = II; const T d = zt * vt[0][i] + zn * vn[0][i]; dx[i] = d + pair_xchg(d); });
   } else {
@@ -725,16 +730,17 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
   T Ma[S::NV];   // M qacc: formed once, then carried along the accepted steps (Ma += alpha * M sr) -- by the iteration itself when it searched,
                  // otherwise (LAZY) at its end and only if another iteration will read it
   sym_matvec<T, S>(M, qacc, Ma);
-  bool ma_dirty = false;   // wave-uniform: a correction moved qacc without updating Ma (and, LAZY, the step before it was not carried either):
-                           // the next iteration rebuilds Ma from qacc
+  bool ma_dirty = false;   // eager instantiations only (wave-uniform): a correction moved qacc without updating Ma, the next iteration rebuilds it from
+                           // qacc.  LAZY rebuilds Ma at the end of the pass that corrected, behind the exit test
   constexpr int maxit = MAXIT;
   // ("is any lane still iterating": eager, at the top of every iteration; LAZY, once before the loop and at the end of every iteration,
   // where the carry needs the answer anyway)
-  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; it < maxit; ++it) {
+  // (LAZY: the iteration cap is part of the one exit test at the end of the iteration, the loop itself has no condition)
+  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; LAZY || it < maxit; ++it) {
     if constexpr (!LAZY) { if (!REX_WAVE_ANY(!lane_done)) break; }
     T cpx[NC], cpz[NC];   // per-iteration opaque copies of the contact points (see opaque())
     if constexpr (BR) for_slots<SLOTS>([&](auto KK) { constexpr int k = KK; cpx[k] = C.px[k]; cpz[k] = C.pz[k]; opaque(cpx[k]); opaque(cpz[k]); });
-    if (ma_dirty) { sym_matvec<T, S>(M, qacc, Ma); ma_dirty = false; }
+    if constexpr (!LAZY) { if (ma_dirty) { sym_matvec<T, S>(M, qacc, Ma); ma_dirty = false; } }
     REX_COUNT(pass1, 1);
     REX_MARK("pass1");
     REX_PSTAMP(s_0, qacc[0]);
@@ -858,7 +864,7 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     // An iteration that does not search reads nothing of phi but the rows active at alpha = 1 (exact_step, the correction):
     // LAZY leaves M sr, q1 / q2 / d0, d1ref and the phi' / phi'' sums (with their pair exchanges) to the iterations that search.
     // (wave-uniform and scalar: `it` and both parameters are)
-    const bool want_ls = !LAZY || (it >= ls_free && ls_max > 0);
+    const bool want_ls = !LAZY || bool(int(it >= ls_free) & int(ls_max > 0));   // (`&`: one scalar test, no short-circuit branch)
     T Ms[S::NV];
     T q1 = T(0), q2 = T(0);
     unsigned m_lim, m_e1, m_e2, m_e3, m_self;   // rows active at the last evaluated alpha
@@ -961,15 +967,7 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; if constexpr (!LAZY) Ma[II] += a * Ms[II];
                                         amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);   // stagnation at rounding level
-    // carry (LAZY, after an iteration that did not search): Ma += a M sr, taken only where a further iteration reads it -- not when the wave is
-    // done, and not before a correction (ma_dirty rebuilds Ma then, so `sr` and `a` are dead across that block)
-    bool go = true;   // LAZY: wave-uniform, some lane is still iterating
-    auto carry = [&]() {
-      if constexpr (LAZY) {
-        go = REX_WAVE_ANY(!lane_done);
-        if (go && !want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
-      }
-    };
+    bool corrected = false;   // wave-uniform: the correction block ran (it moves qacc without updating Ma)
     REX_PSTAMP(s_u, qacc[0] + amax + smax);
     REX_PACC(10, s_d, s_u);
     // ---- one-group correction (straight-line instantiation) ---------------------------------------------------------
@@ -998,8 +996,9 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
       // that: + 1 % hopper, + 5 % walker2d, + 8 % half-cheetah.)  corr: 1 = one group (round 2), 2 = two groups.
       const CorrPlan<SPLIT> plan(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), corr, !lane_done && a == T(1));
       bool can = plan.can;
-      if (REX_WAVE_ANY(can)) {
-        const bool two = SPLIT && REX_WAVE_ANY(plan.two);
+      // both ballots ahead of the ONE branch into the block (`two` selects the coupled form inside corr_step)
+      const bool any_can = REX_WAVE_ANY(can), two = SPLIT && REX_WAVE_ANY(plan.two);
+      if (any_can) {
         T jt1[NC], jn1[NC];
         for_slots<SLOTS>([&](auto KK) { constexpr int k = KK; jt1[k] = lt[k] + lvt[k]; jn1[k] = ln[k] + lvn[k]; });   // J x1 (alpha = 1)
         auto build = [&](unsigned vp, CorrGroup<T, S>& g) {
@@ -1047,16 +1046,25 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
         lane_done = lane_done || (can && ok2);
         // x2 was computed for the set at x1: that is what the next gradient pass compares with
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3;
-        ma_dirty = true;
         REX_COUNT(nocon, 1);   // (diagnostic builds: slot "nocon" counts the correction trips of the wave)
-        if constexpr (LAZY) go = REX_WAVE_ANY(!lane_done);
-      } else carry();
-    } else carry();
+        corrected = true;
+        if constexpr (!LAZY) ma_dirty = true;
+      }
+    }
     REX_PSTAMP(s_2, qacc[0] + amax);
     REX_PACC(6, s_1, s_2); REX_PACC(11, s_u, s_2);
     st.iters = it + 1;
-    if constexpr (LAZY) { if (it == MAXIT - 1) st.capped = go; if (!go) break; }
-    else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
+    if constexpr (LAZY) {
+      // ONE place decides whether the wave iterates on, for the pass that corrected and the pass that did not; only then is Ma brought up to
+      // date for the next pass: rebuilt from qacc after a correction (the same M qacc an `ma_dirty` flag used to ask for at the top of the next
+      // pass, with a test in every pass), carried (Ma += a M sr) after a pass that did not search (one that searched has carried already)
+      const bool go = REX_WAVE_ANY(!lane_done);
+      const bool last = it == MAXIT - 1;
+      if (last) st.capped = go;
+      if (bool(int(!go) | int(last))) break;
+      if (corrected) sym_matvec<T, S>(M, qacc, Ma);
+      else if (!want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
+    } else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
   }
   return st;
 }
@@ -1364,7 +1372,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
   T Ma[S::NV];
   sym_matvec<T, S>(M, qacc, Ma);
   bool ma_dirty = false;
-  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; it < MAXIT; ++it) {   // (loop control: see solve_newton)
+  if (!LAZY || REX_WAVE_ANY(!lane_done)) for (int it = 0; LAZY || it < MAXIT; ++it) {   // (loop control: see solve_newton)
     if constexpr (!LAZY) { if (!REX_WAVE_ANY(!lane_done)) break; }
     // A later iteration walks the units / capsule-capsule rows of the lanes that are STILL ITERATING only: a wave repeats a pass for one or two
     // of its lanes, and the pass costs per listed unit.  (A unit another lane owns adds exact zeros to this lane's sums: same bits either way.)
@@ -1383,7 +1391,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
       um = __builtin_amdgcn_readfirstlane(um); ums = __builtin_amdgcn_readfirstlane(ums);
 #endif
     }
-    if (ma_dirty) { sym_matvec<T, S>(M, qacc, Ma); ma_dirty = false; }
+    if constexpr (!LAZY) { if (ma_dirty) { sym_matvec<T, S>(M, qacc, Ma); ma_dirty = false; } }
     REX_COUNT(pass1, 1);
     // ---- gradient, active edges and the Hessian's unit blocks in ONE walk over the list --------------------------------------------------------
     // (the Hessian block of a unit needs only that unit's own active edges; a solve whose last walk finds every lane converged built its
@@ -1485,7 +1493,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
     // ---- line search on phi(alpha): J sr of every listed unit into the column and phi'(1) in the same walk ------------------------------------
     // (an iteration that does not search only needs the rows active at alpha = 1, and J sr in the column for the correction and for a later
     // search: LAZY leaves the sums to the iterations that search -- solve_newton)
-    const bool want_ls = !LAZY || (it >= ls_free && ls_max > 0);
+    const bool want_ls = !LAZY || bool(int(it >= ls_free) & int(ls_max > 0));   // (`&`: one scalar test, no short-circuit branch)
     T Ms[S::NV];
     T q1 = T(0), q2 = T(0), d0 = T(0);
     if (want_ls) {
@@ -1595,13 +1603,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
     static_for<0, S::NV>([&](auto II) { qacc[II] += a * sr[II]; if constexpr (!LAZY) Ma[II] += a * Ms[II];
                                         amax = max_t(amax, abs_t(qacc[II])); smax = max_t(smax, abs_t(a * sr[II])); });
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);
-    bool go = true;   // LAZY: wave-uniform, some lane is still iterating
-    auto carry = [&]() {   // (solve_newton: the carry of Ma after an iteration that did not search, only where another iteration reads it)
-      if constexpr (LAZY) {
-        go = REX_WAVE_ANY(!lane_done);
-        if (go && !want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
-      }
-    };
+    bool corrected = false;   // (loop tail: see solve_newton)
     // ---- one-group correction (see solve_newton): one joint limit or the edges of ONE unit toggled along a full step ----------------------
     {
       REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
@@ -1613,8 +1615,9 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
       constexpr bool SPLIT = CMODE != 0;
       const CorrPlan<SPLIT> plan(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), corr, !lane_done && a == T(1) && m_self == self_on);
       bool can = plan.can;
-      if (REX_WAVE_ANY(can)) {
-        const bool two = SPLIT && REX_WAVE_ANY(plan.two);
+      // both ballots ahead of the ONE branch into the block (`two` selects the coupled form inside corr_step)
+      const bool any_can = REX_WAVE_ANY(can), two = SPLIT && REX_WAVE_ANY(plan.two);
+      if (any_can) {
         auto build = [&](unsigned vp, CorrGroup<T, S>& g) {
           const unsigned my_lim = plan.my_lim(vp), my_slots = plan.my_slots(vp);
           static_for<0, S::NV>([&](auto II) { g.Ut[II] = T(0); g.Un[II] = T(0); });
@@ -1682,14 +1685,20 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
         REX_STAT_CORRECTION(can, ok2);
         lane_done = lane_done || (can && ok2);
         p_lim = can ? m_lim : p_lim; p_e1 = can ? m_e1 : p_e1; p_e2 = can ? m_e2 : p_e2; p_e3 = can ? m_e3 : p_e3; p_self = can ? m_self : p_self;
-        ma_dirty = true;
         REX_COUNT(nocon, 1);
-        if constexpr (LAZY) go = REX_WAVE_ANY(!lane_done);
-      } else carry();
+        corrected = true;
+        if constexpr (!LAZY) ma_dirty = true;
+      }
     }
     st.iters = it + 1;
-    if constexpr (LAZY) { if (it == MAXIT - 1) st.capped = go; if (!go) break; }
-    else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
+    if constexpr (LAZY) {
+      const bool go = REX_WAVE_ANY(!lane_done);
+      const bool last = it == MAXIT - 1;
+      if (last) st.capped = go;
+      if (bool(int(!go) | int(last))) break;
+      if (corrected) sym_matvec<T, S>(M, qacc, Ma);
+      else if (!want_ls) { sym_matvec<T, S>(M, sr, Ms); static_for<0, S::NV>([&](auto II) { Ma[II] += a * Ms[II]; }); }
+    } else { if (it == MAXIT - 1) st.capped = REX_WAVE_ANY(!lane_done); }
   }
   return st;
 }
