@@ -3,6 +3,7 @@
 #pragma once
 #include "device_rng.hpp"
 #include "planar_model.hpp"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------
 // planar MuJoCo-style envs
@@ -17,6 +18,21 @@ __device__ __forceinline__ void load_geom(const DevState& s, unsigned i, const P
   } else {
     G = uniform;
   }
+}
+
+// The wave-uniform model block of the two-lanes-per-env hopper kernel, as per-lane register values: passed through opaque() once per launch,
+// a field can no longer be traced back to the kernel-argument segment.  Left there, the compiler re-reads it in every forward-dynamics
+// evaluation (a scalar load and a wait with nothing to hide behind, about six per evaluation) once its ~100 scalar registers run out; the
+// kernel has vector registers to spare (one wave per SIMD).  Same values, same operations: same bits.  The solref / solimp parameters
+// stay scalar (pinned as well the kernel measured slower, profiles/HISTORY.md), and so does everything that feeds a scalar branch.
+template <class S>
+__device__ __forceinline__ void pin_uniform(PlanarGeom<float, S>& G) {
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ;   // mass_and_bias and the f vector
+    opaque(G.ja[j][0]); opaque(G.ja[j][1]); opaque(G.co[j][0]); opaque(G.co[j][1]); opaque(G.iyy[j]);
+    opaque(G.armature[j]); opaque(G.damping[j]); opaque(G.stiffness[j]); });
+  static_for<0, S::NG>([&](auto GG) { constexpr int g = GG;   // kinematics and detect_constraints
+    opaque(G.e1[g][0]); opaque(G.e1[g][1]); opaque(G.e2[g][0]); opaque(G.e2[g][1]); opaque(G.radius[g]); });
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; opaque(G.tran_invw[j]); opaque(G.dof_invw[j]); });
 }
 
 // observation: concat(qpos[1:], qvel) (random_hopper.py:100-110, random_half_cheetah.py:112-121,
@@ -141,8 +157,13 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
     __shared__ float slot_lds[SlotMem<float, S, PAIR>::WORDS];
     slot_col = slot_lds + threadIdx.x;
   }
+  // (the pinned instantiation also takes the solver parameters as a copy by value, every other one the argument itself: with the copy the
+  // compiler lays this kernel out 0.5 us faster -- measured, not traced to instructions, profiles/HISTORY.md)
+  constexpr bool PIN = PAIR && !ROLLED && S::KIND == 1;
+  std::conditional_t<PIN, SolParams<float>, const SolParams<float>&> spv = sp;
+  if constexpr (PIN) pin_uniform<S>(G);
 #pragma unroll 1
-  for (int f = 0; f < S::FRAME_SKIP; f++) capped |= substep<float, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, f > 0, slot_col);   // do_simulation, jinja_mujoco_env.py:170-173
+  for (int f = 0; f < S::FRAME_SKIP; f++) capped |= substep<float, S, PAIR, GEN>(q, v, ctrl, G, P, spv, acc, f > 0, slot_col);   // do_simulation, jinja_mujoco_env.py:170-173
   if (PAIR && (threadIdx.x & 1u)) return;   // the even lane of a pair writes the results and runs the fused reset
   // the output addresses are formed from an opaque copy of the lane index: formed from `i`, the compiler computes all of them
   // next to the loads at the top, carries them through the solver, spills them and reloads each with a wait of its own
