@@ -3,7 +3,7 @@
 // under: with auto-reset and dr_training on, the step launch that finishes an episode has already stored the next episode's task over
 // the lane's xi rows, so the handle keeps a per-lane shadow of the task in force when the lane's current episode began.
 //
-// Two launches per rex_eplog_step on blocks of vecnorm::BLOCK lanes, one thread per env:
+// Two launches per rex_eplog_step on blocks of postpass::BLOCK lanes, one thread per env:
 //   1. el_count_kernel   every wave ballots done != 0; the block writes its popcount to counts[blockIdx.x].  Thread 0 of block 0 also
 //                        commits the bookkeeping of the previous call (total_cur = total_next, serial_cur = serial_next).
 //   2. el_append_kernel  every block forms its base = total_cur + sum(counts[0 .. blockIdx.x)) with a block-parallel sum (integers: any
@@ -22,11 +22,11 @@
 #pragma once
 #include <cstdint>
 
-#include "vecnorm.hpp"
+#include "postpass.hpp"
 
 namespace eplog {
 
-constexpr int BLOCK = vecnorm::BLOCK;   // lanes (envs) per block
+constexpr int BLOCK = postpass::BLOCK;   // lanes (envs) per block
 constexpr int WAVE = 64;
 constexpr int WAVES = BLOCK / WAVE;
 constexpr int MAX_TASK = 32;            // rows of a task (the kernels' MAX_XI)

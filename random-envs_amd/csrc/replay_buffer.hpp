@@ -4,9 +4,9 @@
 // transition and read at random many times, so the storage is TRANSITION-MAJOR -- obs / next_obs [T][B][obs_dim], action [T][B][act_dim],
 // reward / done / timeout [T][B], transition id s = t * B + b -- and the transpose from the SoA step buffers belongs to the add.
 //
-//   rb_add_kernel     one launch per step on the grid (tiles of A_ENVS envs, row groups of at most A_ROWS rows over obs | next_obs | action):
-//                     lane = env for the coalesced SoA row reads, the tile is staged in LDS with an odd stride and written with consecutive
-//                     lanes on consecutive words of a transition's row.  The next_obs groups take terminal_obs on the done lanes; the blocks
+//   rb_add_kernel     one launch per step on the grid (tiles of TILE_ITEMS envs, row groups of at most TILE_ROWS rows over obs | next_obs |
+//                     action): lane = env for the coalesced SoA row reads, the tile goes through postpass.hpp's LDS tile and is written with
+//                     consecutive lanes on consecutive words of a transition's row.  The next_obs groups take terminal_obs on the done lanes; the blocks
 //                     of group 0 also copy the reward, done and timeout rows.
 //   rb_sample_kernel  serves rex_rbuf_sample and rex_rbuf_gather.  A block takes S_BLOCK samples, a wave W_SAMPLES of them: lane k of the wave
 //                     draws (Philox4x32-10, multiply-shift) or loads the id of the wave's k-th sample once and writes its [n] outputs; the
@@ -16,23 +16,22 @@
 //                     LDS); a lane keeps those of its four columns in registers across the block's samples.
 // No float atomics, no grid-wide sync, no host state between launches; slot, fill level, seed and draw number are arguments.
 //
-// The Philox block, the id map, the id guard, the next_obs select, done_out, the tile / LDS / column addressing and the normalise calls are
+// The Philox block, the id map, the next_obs select, done_out, the column addressing and the normalise calls are
 // __host__ __device__: tests/host_harness/rbuf_host.cpp drives them with g++ in grid order.
 #pragma once
-#include "vecnorm.hpp"
+#include "postpass.hpp"
+#include "vecnorm.hpp"   // Norm: inv_std and normalise of the running statistics
 
 namespace rbuf {
 
-constexpr int BLOCK = 256;             // threads per block (four waves)
-constexpr int A_ENVS = 64;             // envs per tile of the add: lane = env
-constexpr int A_ROWS = 64;             // rows staged in LDS at a time
-constexpr int A_STRIDE = A_ROWS + 1;   // odd stride: lane l of a wave writes bank (l + row) % 64
+using postpass::BLOCK, postpass::F4, postpass::U4, postpass::TILE_ITEMS, postpass::TILE_ROWS, postpass::row_groups, postpass::guard_id;
+using Tr = postpass::Id;               // a transition id behind the guard: never turned into an address when it is not ok
+
+constexpr int A_ENVS = TILE_ITEMS, A_ROWS = TILE_ROWS, A_STRIDE = postpass::TILE_STRIDE;   // the tile's names before postpass.hpp, for harness sources written then
 constexpr int W_SAMPLES = 2;           // samples per wave of the sample launch
 constexpr int S_BLOCK = W_SAMPLES * (BLOCK / 64);   // samples per block
 constexpr int LANE_COLS = 4;           // columns of a row a lane holds per pass: one 16-byte access, or four 4-byte ones 64 words apart
 constexpr int PASS_COLS = 64 * LANE_COLS;           // columns a wave covers per pass = one column per thread of the block
-
-struct alignas(16) U4 { uint32_t x, y, z, w; };
 
 // The caller's buffers (rex_rbuf_buffers of include/rex.h) with the handle's sizes beside them.  Rows are copied as 4-byte words.
 struct Buf {
@@ -75,15 +74,6 @@ VN_HD inline uint64_t sample_bits(uint64_t seed, uint64_t draw, uint64_t j) {
 // ... mapped to [0, N): the high half of u * N (bias at most N / 2^64); with replacement, a function of (seed, draw, N, j) only
 VN_HD inline long long sample_id(uint64_t seed, uint64_t draw, uint64_t j, long long N) { return (long long)mulhi64(sample_bits(seed, draw, j), (uint64_t)N); }
 
-// A transition id outside [0, T * B) is not ok and is never turned into an address.
-struct Tr { long long s; bool ok; };
-VN_HD inline Tr guard_id(long long s, long long T, long long B) {
-  Tr o;
-  o.ok = s >= 0 && s < T * B;
-  o.s = o.ok ? s : 0;
-  return o;
-}
-
 // SB3's dones * (1 - timeouts): a time-limit end still bootstraps
 VN_HD inline float done_out(uint8_t done, uint8_t timeout) { return (done && !timeout) ? 1.0f : 0.0f; }
 
@@ -95,10 +85,8 @@ struct AddSrc {
   const uint8_t* truncated;       // may be null
 };
 
-VN_HD inline int row_groups(int dim) { return (dim + A_ROWS - 1) / A_ROWS; }
 VN_HD inline int add_groups(int obs_dim, int act_dim) { return 2 * row_groups(obs_dim) + row_groups(act_dim); }
-VN_HD inline long long add_tiles(long long B) { return (B + A_ENVS - 1) / A_ENVS; }
-VN_HD inline int tile_envs(long long B, long long tile) { const long long left = B - tile * A_ENVS; return left < A_ENVS ? (int)left : A_ENVS; }
+VN_HD inline long long add_tiles(long long B) { return (B + TILE_ITEMS - 1) / TILE_ITEMS; }
 
 // Row group g of the add launch: the groups of obs, then those of next_obs, then those of action
 enum { F_OBS = 0, F_NEXT = 1, F_ACTION = 2 };
@@ -108,13 +96,10 @@ VN_HD inline Group add_group(int g, int obs_dim, int act_dim) {
   Group o;
   o.field = g < og ? F_OBS : (g < 2 * og ? F_NEXT : F_ACTION);
   o.dim = o.field == F_ACTION ? act_dim : obs_dim;
-  o.r0 = (g - o.field * og) * A_ROWS;
-  o.nr = o.dim - o.r0 < A_ROWS ? o.dim - o.r0 : A_ROWS;
+  o.r0 = (g - o.field * og) * TILE_ROWS;
+  o.nr = postpass::group_rows(o.dim, o.r0);
   return o;
 }
-VN_HD inline int lds_slot(int env, int row) { return env * A_STRIDE + row; }
-// word e of a staged tile of `nr` rows: which env, which row
-VN_HD inline void tile_elem(int e, int nr, int* env, int* row) { *env = e / nr; *row = e - *env * nr; }
 
 // the SoA word of row `row` of lane b that group `g` stores: next_obs takes the terminal observation on the done lanes
 VN_HD inline uint32_t add_word(const AddSrc& s, const Group& g, int row, long long b, long long B) {
@@ -127,34 +112,28 @@ VN_HD inline uint32_t add_word(const AddSrc& s, const Group& g, int row, long lo
 // Thread t's share of staging block (tile, group): lane = env, the block's waves take the group's rows in turn
 VN_HD inline void thread_add_stage(const Buf& b, const AddSrc& s, long long tile, int group, int t, uint32_t* lds) {
   const int lane = t & 63, wave = t >> 6;
-  if (lane >= tile_envs(b.B, tile)) return;
+  if (lane >= postpass::tile_items(b.B, tile)) return;
   const Group g = add_group(group, b.obs_dim, b.act_dim);
-  const long long env = tile * A_ENVS + lane;
-  for (int rr = wave; rr < g.nr; rr += BLOCK / 64) lds[lds_slot(lane, rr)] = add_word(s, g, g.r0 + rr, env, b.B);
+  const long long env = tile * TILE_ITEMS + lane;
+  for (int rr = wave; rr < g.nr; rr += BLOCK / 64)   // (postpass::tile_stage's loop, written out: through the lambda the kernel compiles to other code)
+    lds[postpass::tile_slot(lane, rr)] = add_word(s, g, g.r0 + rr, env, b.B);
 }
 
 // ... of writing it to slot `slot`: consecutive threads on consecutive words of a transition's row
-VN_HD inline void thread_write_tile(uint32_t* dst, const Group& g, size_t s0, int ne, int t, const uint32_t* lds) {
-  for (int e = t; e < ne * g.nr; e += BLOCK) {
-    int env, rr;
-    tile_elem(e, g.nr, &env, &rr);
-    dst[(s0 + env) * (size_t)g.dim + g.r0 + rr] = lds[lds_slot(env, rr)];
-  }
-}
 VN_HD inline void thread_add_write(const Buf& b, long long slot, long long tile, int group, int t, const uint32_t* lds) {
   const Group g = add_group(group, b.obs_dim, b.act_dim);
-  const int ne = tile_envs(b.B, tile);
-  const size_t s0 = (size_t)slot * (size_t)b.B + (size_t)tile * A_ENVS;
-  if (g.field == F_OBS) thread_write_tile(b.obs, g, s0, ne, t, lds);              // a branch per field: a pointer picked by index would
-  else if (g.field == F_NEXT) thread_write_tile(b.next_obs, g, s0, ne, t, lds);   // be read back from a private copy of the three
-  else thread_write_tile(b.action, g, s0, ne, t, lds);
+  const int ne = postpass::tile_items(b.B, tile);
+  const size_t s0 = (size_t)slot * (size_t)b.B + (size_t)tile * TILE_ITEMS;
+  if (g.field == F_OBS) postpass::tile_write(b.obs, g.dim, g.r0, g.nr, s0, ne, t, lds);              // a branch per field: a pointer picked by
+  else if (g.field == F_NEXT) postpass::tile_write(b.next_obs, g.dim, g.r0, g.nr, s0, ne, t, lds);   // index would be read back from a
+  else postpass::tile_write(b.action, g.dim, g.r0, g.nr, s0, ne, t, lds);                            // private copy of the three
 }
 
 // ... of the [T][B] rows (the blocks of group 0 only): wave 0 reward, wave 1 done, wave 2 timeout
 VN_HD inline void thread_add_flat(const Buf& b, const AddSrc& s, long long slot, long long tile, int t) {
   const int lane = t & 63, wave = t >> 6;
-  if (lane >= tile_envs(b.B, tile)) return;
-  const size_t env = (size_t)tile * A_ENVS + lane, o = (size_t)slot * (size_t)b.B + env;
+  if (lane >= postpass::tile_items(b.B, tile)) return;
+  const size_t env = (size_t)tile * TILE_ITEMS + lane, o = (size_t)slot * (size_t)b.B + env;
   if (wave == 0) b.reward[o] = s.reward[env];
   else if (wave == 1) b.done[o] = s.done[env] != 0;
   else if (wave == 2) b.timeout[o] = s.truncated ? s.truncated[env] != 0 : 0;
@@ -218,13 +197,13 @@ VN_HD inline void lane_normalise(const float* src, float* dst, int dim, int c0, 
   if (vec) {
     const int c = lane_col(c0, lane, 0, true);
     if (c < dim) {
-      vecnorm::F4 q{0.0f, 0.0f, 0.0f, 0.0f};
+      F4 q{0.0f, 0.0f, 0.0f, 0.0f};
       if (ok) {
-        q = *reinterpret_cast<const vecnorm::F4*>(src + c);
+        q = *reinterpret_cast<const F4*>(src + c);
         q.x = vecnorm::normalise(q.x, mean[0], inv[0], clip); q.y = vecnorm::normalise(q.y, mean[1], inv[1], clip);
         q.z = vecnorm::normalise(q.z, mean[2], inv[2], clip); q.w = vecnorm::normalise(q.w, mean[3], inv[3], clip);
       }
-      *reinterpret_cast<vecnorm::F4*>(dst + c) = q;
+      *reinterpret_cast<F4*>(dst + c) = q;
     }
   } else {
 #pragma unroll
@@ -277,7 +256,7 @@ VN_HD inline void lane_action(const Buf& b, const Out& o, long long j, const Tr&
 struct AddParams { Buf buf; AddSrc src; long long slot; };
 
 __global__ __launch_bounds__(BLOCK) void rb_add_kernel(AddParams p) {
-  __shared__ uint32_t lds[A_ENVS * A_STRIDE];
+  __shared__ uint32_t lds[postpass::TILE_WORDS];
   const long long tile = blockIdx.x;
   const int group = blockIdx.y, t = threadIdx.x;
   if (group == 0) thread_add_flat(p.buf, p.src, p.slot, tile, t);

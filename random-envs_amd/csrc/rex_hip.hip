@@ -3,7 +3,8 @@
 // The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
 // math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp (the last also owns the pair kernel's view of the SoA state: load_lane /
-// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp and replay_buffer.hpp.  Profiling probes
+// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp, replay_buffer.hpp and eplog.hpp over
+// postpass.hpp (their common block, chunk walk, LDS tile and id guard).  Profiling probes
 // live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.
@@ -31,6 +32,7 @@
 
 #include "../../include/rex.h"
 #include "launch_shape.hpp"
+#include "postpass.hpp"
 #include "vecnorm.hpp"
 #include "rollout.hpp"
 #include "replay_buffer.hpp"
@@ -64,6 +66,9 @@ extern "C" const char* rex_version(void) { return "rex-hip 0.1 (gfx950)"; }
 // and fails on an exported function that takes a handle and launches / copies without it.
 #define REX_ENTER(h, fn)                                                    \
   do { if (!(h)) return set_err(REX_ERR_ARG, fn ": null handle"); HIP_TRY(hipSetDevice((h)->device)); } while (0)
+// ... of an opt-in post-pass, after REX_ENTER: the handle's block `mem` exists only once `enabler_name` has been called
+#define REX_NEEDS(h, mem, fn, enabler_name) \
+  do { if (!(h)->mem) return set_err(REX_ERR_STATE, fn ": " enabler_name " has not been called on this handle"); } while (0)
 
 // Environment knobs.  They select among the product's own launch shapes and solver schedules (every choice converges to the same
 // minimiser) and exist for A/B measurements and for the parity tests that hold every shape to the oracle.  A stray variable
@@ -672,6 +677,23 @@ static int copy_rows(float* dst, const float* src, int rows, long long B, hipStr
   HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * rows * (size_t)B, hipMemcpyDeviceToDevice, st));
   return REX_OK;
 }
+// grid_fits: a block count one launch takes in x.  read_counter: a device counter to the host once the device has drained, optionally
+// cleared.  move_lanes: one array of a get / set pair of per-lane state, n items towards `user` (get) or towards `mine` (set).
+static bool grid_fits(long long blocks) { return blocks <= 0x7fffffffLL; }
+static int read_counter(unsigned long long* ptr, int64_t* out, int clear) {
+  unsigned long long v = 0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&v, ptr, sizeof v, hipMemcpyDeviceToHost));
+  *out = (int64_t)v;
+  if (clear) HIP_TRY(hipMemset(ptr, 0, sizeof v));
+  return REX_OK;
+}
+template <class T>
+static int move_lanes(bool get, T* mine, T* user, long long n, hipStream_t st) {   // (set: `user` is only read)
+  HIP_TRY(hipMemcpyAsync(get ? user : mine, get ? mine : user, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, st));
+  return REX_OK;
+}
+
 extern "C" int rex_get_state(rex_t* h, float* qpos, float* qvel, void* stream) {
   REX_ENTER(h, "rex_get_state");
   if (!qpos || !qvel) return set_err(REX_ERR_ARG, "rex_get_state: null argument");
@@ -784,23 +806,20 @@ extern "C" int rex_read_timing(rex_t* h, float* ms_out, int max_n) {
 // ------------------------------------------------------------------------------------------
 // episode bookkeeping, lane export, side-effect-free xi draws
 // ------------------------------------------------------------------------------------------
+static int move_counters_state(rex_env* h, bool get, int32_t* t, uint32_t* episode, uint8_t* done, hipStream_t st) {
+  if (int rc = move_lanes(get, h->dev.t, t, h->B, st)) return rc;
+  if (int rc = move_lanes(get, h->dev.episode, episode, h->B, st)) return rc;
+  return move_lanes(get, h->dev.done, done, h->B, st);
+}
 extern "C" int rex_get_counters_state(rex_t* h, int32_t* t, uint32_t* episode, uint8_t* done, void* stream) {
   REX_ENTER(h, "rex_get_counters_state");
   if (!t || !episode || !done) return set_err(REX_ERR_ARG, "rex_get_counters_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(t, h->dev.t, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(episode, h->dev.episode, sizeof(unsigned) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(done, h->dev.done, B, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_counters_state(h, true, t, episode, done, (hipStream_t)stream);
 }
 extern "C" int rex_set_counters_state(rex_t* h, const int32_t* t, const uint32_t* episode, const uint8_t* done, void* stream) {
   REX_ENTER(h, "rex_set_counters_state");
   if (!t || !episode || !done) return set_err(REX_ERR_ARG, "rex_set_counters_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(h->dev.t, t, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->dev.episode, episode, sizeof(unsigned) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->dev.done, done, B, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_counters_state(h, false, const_cast<int32_t*>(t), const_cast<uint32_t*>(episode), const_cast<uint8_t*>(done), (hipStream_t)stream);
 }
 extern "C" int rex_get_aux(rex_t* h, float* aux, void* stream) {
   REX_ENTER(h, "rex_get_aux");
@@ -855,9 +874,6 @@ extern "C" int rex_sample_task(rex_t* h, float* xi_out, uint64_t draw_index, voi
 // ------------------------------------------------------------------------------------------
 // observation / reward normalisation and episode statistics (vecnorm.hpp): an opt-in post-pass of two launches
 // ------------------------------------------------------------------------------------------
-#define REX_NORM_ON(h, fn) \
-  do { if (!(h)->norm_mem) return set_err(REX_ERR_STATE, fn ": rex_norm_enable has not been called on this handle"); } while (0)
-
 static int norm_init_state(rex_env* h) {   // mean 0, var 1, count 1e-4 (RunningMeanStd.__init__), everything else 0
   const vecnorm::Params& p = h->norm;
   const size_t R = (size_t)p.rows;
@@ -881,7 +897,7 @@ extern "C" int rex_norm_enable(rex_t* h, const rex_norm_config* cfg) {
   const int R = h->dims.obs_dim + 1;
   const size_t B = (size_t)h->B;
   vecnorm::Params p{};
-  p.B = h->B; p.rows = R; p.chunks = vecnorm::chunk_count(h->B, R); p.tpc = vecnorm::tiles_per_chunk(h->B, p.chunks);
+  p.B = h->B; p.rows = R; p.chunks = postpass::chunk_count(h->B, R); p.tpc = postpass::tiles_per_chunk(h->B, p.chunks);
   if (!h->norm_mem) {
     const size_t n_dbl = 3 * (size_t)R + 3 * (size_t)R + 4 * (size_t)R * p.chunks + 3 * (size_t)p.chunks + 3 + 1 + 2 * B;
     HIP_TRY(hipMalloc(&h->norm_mem, sizeof(double) * n_dbl + sizeof(int32_t) * B));
@@ -902,12 +918,10 @@ extern "C" int rex_norm_enable(rex_t* h, const rex_norm_config* cfg) {
 
 extern "C" int rex_norm_set_training(rex_t* h, int flag) {
   if (!h) return set_err(REX_ERR_ARG, "rex_norm_set_training: null handle");
-  REX_NORM_ON(h, "rex_norm_set_training");
+  REX_NEEDS(h, norm_mem, "rex_norm_set_training", "rex_norm_enable");
   h->norm_cfg.training = flag ? 1 : 0;
   return REX_OK;
 }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // moments launch over rows [m_row0, m_row0 + m_rows) (none when m_rows == 0), then the normalise launch over rows [n_row0, rows)
 static int launch_norm(vecnorm::Params p, int m_row0, int m_rows, int n_row0, hipStream_t st) {
@@ -930,13 +944,13 @@ static vecnorm::Params norm_call_params(const rex_env* h, int mode, const float*
   p.upd_obs = (c.training && p.norm_obs) ? 1 : 0; p.upd_ret = (c.training && c.norm_reward) ? 1 : 0;
   p.gamma = c.gamma; p.eps = c.epsilon; p.clip_obs = c.clip_obs; p.clip_reward = c.clip_reward;
   p.obs_in = obs_in; p.obs_out = obs_out;
-  p.vec_ok = (h->B % vecnorm::VEC == 0 && aligned16(obs_in) && aligned16(obs_out)) ? 1 : 0;
+  p.vec_ok = (h->B % postpass::VEC == 0 && postpass::all_aligned16(obs_in, obs_out)) ? 1 : 0;
   return p;
 }
 
 extern "C" int rex_norm_reset(rex_t* h, const uint8_t* mask, const float* obs_in, float* obs_out, void* stream) {
   REX_ENTER(h, "rex_norm_reset");
-  REX_NORM_ON(h, "rex_norm_reset");
+  REX_NEEDS(h, norm_mem, "rex_norm_reset", "rex_norm_enable");
   if (!obs_in != !obs_out) return set_err(REX_ERR_ARG, "rex_norm_reset: obs_in and obs_out go together (both NULL skips the observation rows)");
   vecnorm::Params p = norm_call_params(h, vecnorm::MODE_RESET, obs_in, obs_out);
   p.mask = mask;
@@ -946,7 +960,7 @@ extern "C" int rex_norm_reset(rex_t* h, const uint8_t* mask, const float* obs_in
 extern "C" int rex_norm_step(rex_t* h, const float* obs_in, const float* reward_in, const uint8_t* done, const float* term_obs_in,
                              float* obs_out, float* reward_out, float* term_obs_out, double* ep_return_out, int32_t* ep_len_out, void* stream) {
   REX_ENTER(h, "rex_norm_step");
-  REX_NORM_ON(h, "rex_norm_step");
+  REX_NEEDS(h, norm_mem, "rex_norm_step", "rex_norm_enable");
   if (!reward_in || !done) return set_err(REX_ERR_ARG, "rex_norm_step: reward_in and done are required");
   if (!obs_in != !obs_out) return set_err(REX_ERR_ARG, "rex_norm_step: obs_in and obs_out go together (both NULL skips the observation rows)");
   if (!term_obs_in != !term_obs_out) return set_err(REX_ERR_ARG, "rex_norm_step: term_obs_in and term_obs_out go together");
@@ -961,7 +975,7 @@ extern "C" int rex_norm_step(rex_t* h, const float* obs_in, const float* reward_
 
 extern "C" int rex_norm_get_stats(rex_t* h, double* out) {
   REX_ENTER(h, "rex_norm_get_stats");
-  REX_NORM_ON(h, "rex_norm_get_stats");
+  REX_NEEDS(h, norm_mem, "rex_norm_get_stats", "rex_norm_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_norm_get_stats: null argument");
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, h->norm.stats, sizeof(double) * 3 * h->norm.rows, hipMemcpyDeviceToHost));
@@ -969,7 +983,7 @@ extern "C" int rex_norm_get_stats(rex_t* h, double* out) {
 }
 extern "C" int rex_norm_set_stats(rex_t* h, const double* in) {
   REX_ENTER(h, "rex_norm_set_stats");
-  REX_NORM_ON(h, "rex_norm_set_stats");
+  REX_NEEDS(h, norm_mem, "rex_norm_set_stats", "rex_norm_enable");
   if (!in) return set_err(REX_ERR_ARG, "rex_norm_set_stats: null argument");
   const int R = h->norm.rows;
   for (int r = 0; r < R; r++)
@@ -980,30 +994,28 @@ extern "C" int rex_norm_set_stats(rex_t* h, const double* in) {
   return REX_OK;
 }
 
+static int move_norm_lane_state(rex_env* h, bool get, double* ret, double* ep_return, int32_t* ep_len, hipStream_t st) {
+  const vecnorm::LaneState& ls = h->norm.lanes;
+  if (int rc = move_lanes(get, ls.ret, ret, h->B, st)) return rc;
+  if (int rc = move_lanes(get, ls.ep_return, ep_return, h->B, st)) return rc;
+  return move_lanes(get, ls.ep_len, ep_len, h->B, st);
+}
 extern "C" int rex_norm_get_lane_state(rex_t* h, double* ret, double* ep_return, int32_t* ep_len, void* stream) {
   REX_ENTER(h, "rex_norm_get_lane_state");
-  REX_NORM_ON(h, "rex_norm_get_lane_state");
+  REX_NEEDS(h, norm_mem, "rex_norm_get_lane_state", "rex_norm_enable");
   if (!ret || !ep_return || !ep_len) return set_err(REX_ERR_ARG, "rex_norm_get_lane_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(ret, h->norm.lanes.ret, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ep_return, h->norm.lanes.ep_return, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ep_len, h->norm.lanes.ep_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_norm_lane_state(h, true, ret, ep_return, ep_len, (hipStream_t)stream);
 }
 extern "C" int rex_norm_set_lane_state(rex_t* h, const double* ret, const double* ep_return, const int32_t* ep_len, void* stream) {
   REX_ENTER(h, "rex_norm_set_lane_state");
-  REX_NORM_ON(h, "rex_norm_set_lane_state");
+  REX_NEEDS(h, norm_mem, "rex_norm_set_lane_state", "rex_norm_enable");
   if (!ret || !ep_return || !ep_len) return set_err(REX_ERR_ARG, "rex_norm_set_lane_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(h->norm.lanes.ret, ret, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->norm.lanes.ep_return, ep_return, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->norm.lanes.ep_len, ep_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_norm_lane_state(h, false, const_cast<double*>(ret), const_cast<double*>(ep_return), const_cast<int32_t*>(ep_len), (hipStream_t)stream);
 }
 
 extern "C" int rex_norm_read_episodes(rex_t* h, double* out, int clear) {
   REX_ENTER(h, "rex_norm_read_episodes");
-  REX_NORM_ON(h, "rex_norm_read_episodes");
+  REX_NEEDS(h, norm_mem, "rex_norm_read_episodes", "rex_norm_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_norm_read_episodes: null argument");
   unsigned long long nf = 0;
   HIP_TRY(hipDeviceSynchronize());
@@ -1017,9 +1029,6 @@ extern "C" int rex_norm_read_episodes(rex_t* h, double* out, int clear) {
 // ------------------------------------------------------------------------------------------
 // on-policy rollout buffer (rollout.hpp): fused add, GAE, advantage statistics, minibatch gather over caller-owned SoA buffers
 // ------------------------------------------------------------------------------------------
-#define REX_ROLLOUT_ON(h, fn) \
-  do { if (!(h)->rollout_mem) return set_err(REX_ERR_STATE, fn ": rex_rollout_enable has not been called on this handle"); } while (0)
-
 static rollout::Part* rollout_scratch(const rex_env* h) { return (rollout::Part*)h->rollout_mem; }
 static double* rollout_result(const rex_env* h) { return (double*)(rollout_scratch(h) + rollout::MAX_PARTS); }
 static unsigned long long* rollout_bad(const rex_env* h) { return (unsigned long long*)(rollout_result(h) + 4); }
@@ -1048,7 +1057,7 @@ extern "C" int rex_rollout_add(rex_t* h, const rex_rollout_buffers* buf, int64_t
                                const uint8_t* done, const float* value, const float* log_prob, const uint8_t* truncated,
                                const float* terminal_value, double gamma, void* stream) {
   REX_ENTER(h, "rex_rollout_add");
-  REX_ROLLOUT_ON(h, "rex_rollout_add");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_add", "rex_rollout_enable");
   rollout::AddParams p{};
   if (int rc = rollout_buf(h, buf, "rex_rollout_add", &p.buf)) return rc;
   if (t < 0 || t >= buf->T) return set_err(REX_ERR_ARG, "rex_rollout_add: slot %lld outside [0, %lld)", (long long)t, (long long)buf->T);
@@ -1057,13 +1066,12 @@ extern "C" int rex_rollout_add(rex_t* h, const rex_rollout_buffers* buf, int64_t
   p.src = rollout::AddSrc{obs, (const uint32_t*)action, reward, done, value, log_prob, truncated, terminal_value};
   p.slot = t; p.gamma = gamma;
   const int rows = rollout::add_rows(p.buf.obs_dim, p.buf.act_dim);
-  const int chunks = vecnorm::chunk_count(h->B, rows);
-  p.tpc = vecnorm::tiles_per_chunk(h->B, chunks);
+  const int chunks = postpass::chunk_count(h->B, rows);
+  p.tpc = postpass::tiles_per_chunk(h->B, chunks);
   // 16-byte accesses: with B a multiple of 4 every row and every slot of a 16-byte aligned buffer starts 16-byte aligned (the
-  // byte rows: 4-byte aligned, which their 4-byte accesses need)
-  p.vec_ok = (h->B % vecnorm::VEC == 0 && aligned16(obs) && aligned16(action) && aligned16(reward) && aligned16(done) && aligned16(value) &&
-              aligned16(log_prob) && (!truncated || (aligned16(truncated) && aligned16(terminal_value))) && aligned16(buf->obs) &&
-              aligned16(buf->action) && aligned16(buf->reward) && aligned16(buf->value) && aligned16(buf->log_prob) && aligned16(buf->done)) ? 1 : 0;
+  // byte rows: 4-byte aligned, which their 4-byte accesses need); truncated and terminal_value may be null, which counts as aligned
+  p.vec_ok = (h->B % postpass::VEC == 0 && postpass::all_aligned16(obs, action, reward, done, value, log_prob, truncated, terminal_value, buf->obs,
+                                                                   buf->action, buf->reward, buf->value, buf->log_prob, buf->done)) ? 1 : 0;
   hipLaunchKernelGGL(rollout::ro_add_kernel, dim3(chunks, rows), dim3(rollout::BLOCK), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return REX_OK;
@@ -1071,7 +1079,7 @@ extern "C" int rex_rollout_add(rex_t* h, const rex_rollout_buffers* buf, int64_t
 
 extern "C" int rex_rollout_gae(rex_t* h, const rex_rollout_buffers* buf, const float* last_value, double gamma, double lambda, void* stream) {
   REX_ENTER(h, "rex_rollout_gae");
-  REX_ROLLOUT_ON(h, "rex_rollout_gae");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_gae", "rex_rollout_enable");
   rollout::GaeParams p{};
   if (int rc = rollout_buf(h, buf, "rex_rollout_gae", &p.buf)) return rc;
   if (!last_value) return set_err(REX_ERR_ARG, "rex_rollout_gae: null last_value");
@@ -1085,14 +1093,14 @@ extern "C" int rex_rollout_gae(rex_t* h, const rex_rollout_buffers* buf, const f
 
 extern "C" int rex_rollout_adv_stats(rex_t* h, const rex_rollout_buffers* buf, int normalise, void* stream) {
   REX_ENTER(h, "rex_rollout_adv_stats");
-  REX_ROLLOUT_ON(h, "rex_rollout_adv_stats");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_adv_stats", "rex_rollout_enable");
   rollout::Buf b{};
   if (int rc = rollout_buf(h, buf, "rex_rollout_adv_stats", &b)) return rc;
   rollout::StatParams p{};
   p.adv = b.advantage; p.N = b.T * b.B;
-  p.parts = rollout::part_count(p.N); p.tpc = vecnorm::tiles_per_chunk(p.N, p.parts);
+  p.parts = rollout::part_count(p.N); p.tpc = postpass::tiles_per_chunk(p.N, p.parts);
   p.normalise = normalise ? 1 : 0;
-  p.vec_ok = aligned16(b.advantage) ? 1 : 0;
+  p.vec_ok = postpass::aligned16(b.advantage) ? 1 : 0;
   p.scratch = rollout_scratch(h); p.result = rollout_result(h);
   hipLaunchKernelGGL(rollout::ro_moments_kernel, dim3(p.parts), dim3(rollout::BLOCK), 0, (hipStream_t)stream, p);
   hipLaunchKernelGGL(rollout::ro_finish_kernel, dim3(p.normalise ? p.parts : 1), dim3(rollout::BLOCK), 0, (hipStream_t)stream, p);
@@ -1102,7 +1110,7 @@ extern "C" int rex_rollout_adv_stats(rex_t* h, const rex_rollout_buffers* buf, i
 
 extern "C" int rex_rollout_get_adv_stats(rex_t* h, double* out) {
   REX_ENTER(h, "rex_rollout_get_adv_stats");
-  REX_ROLLOUT_ON(h, "rex_rollout_get_adv_stats");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_get_adv_stats", "rex_rollout_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_rollout_get_adv_stats: null argument");
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, rollout_result(h), sizeof(double) * 4, hipMemcpyDeviceToHost));
@@ -1112,18 +1120,18 @@ extern "C" int rex_rollout_get_adv_stats(rex_t* h, double* out) {
 extern "C" int rex_rollout_gather(rex_t* h, const rex_rollout_buffers* buf, const int64_t* index, int64_t n, float* obs_out, void* action_out,
                                   float* advantage_out, float* returns_out, float* value_out, float* log_prob_out, void* stream) {
   REX_ENTER(h, "rex_rollout_gather");
-  REX_ROLLOUT_ON(h, "rex_rollout_gather");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_gather", "rex_rollout_enable");
   rollout::GatherParams p{};
   if (int rc = rollout_buf(h, buf, "rex_rollout_gather", &p.buf)) return rc;
   if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rollout_gather: n must be >= 0 and index given");
   if (n == 0) return REX_OK;
-  const long long blocks = (n + rollout::G_SAMPLES - 1) / rollout::G_SAMPLES;
-  if (blocks > 0x7fffffffLL) return set_err(REX_ERR_ARG, "rex_rollout_gather: n = %lld is more than one launch takes", (long long)n);
+  const long long blocks = (n + postpass::TILE_ITEMS - 1) / postpass::TILE_ITEMS;
+  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "rex_rollout_gather: n = %lld is more than one launch takes", (long long)n);
   p.index = (const long long*)index; p.n = n;
   p.obs_out = (uint32_t*)obs_out; p.action_out = (uint32_t*)action_out;
   p.advantage_out = advantage_out; p.returns_out = returns_out; p.value_out = value_out; p.log_prob_out = log_prob_out;
   p.bad = rollout_bad(h);
-  const unsigned groups = (unsigned)(rollout::row_groups(p.buf.obs_dim) + rollout::row_groups(p.buf.act_dim));
+  const unsigned groups = (unsigned)(postpass::row_groups(p.buf.obs_dim) + postpass::row_groups(p.buf.act_dim));
   hipLaunchKernelGGL(rollout::ro_gather_kernel, dim3((unsigned)blocks, groups), dim3(rollout::BLOCK), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return REX_OK;
@@ -1131,22 +1139,14 @@ extern "C" int rex_rollout_gather(rex_t* h, const rex_rollout_buffers* buf, cons
 
 extern "C" int rex_rollout_read_bad_indices(rex_t* h, int64_t* out, int clear) {
   REX_ENTER(h, "rex_rollout_read_bad_indices");
-  REX_ROLLOUT_ON(h, "rex_rollout_read_bad_indices");
+  REX_NEEDS(h, rollout_mem, "rex_rollout_read_bad_indices", "rex_rollout_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_rollout_read_bad_indices: null argument");
-  unsigned long long v = 0;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(&v, rollout_bad(h), sizeof v, hipMemcpyDeviceToHost));
-  *out = (int64_t)v;
-  if (clear) HIP_TRY(hipMemset(rollout_bad(h), 0, sizeof v));
-  return REX_OK;
+  return read_counter(rollout_bad(h), out, clear);
 }
 
 // ------------------------------------------------------------------------------------------
 // episode ledger (eplog.hpp): finished episodes with the task they ran under, appended to a caller-owned table in two launches
 // ------------------------------------------------------------------------------------------
-#define REX_EPLOG_ON(h, fn) \
-  do { if (!(h)->eplog_mem) return set_err(REX_ERR_STATE, fn ": rex_eplog_enable has not been called on this handle"); } while (0)
-
 static_assert(MAX_XI <= eplog::MAX_TASK, "a task fits the ledger's row map");
 
 static int launch_eplog_sync(const rex_env* h, const uint8_t* mask, int restart, hipStream_t st) {
@@ -1188,7 +1188,7 @@ extern "C" int rex_eplog_enable(rex_t* h, const rex_eplog_buffers* buf) {
 
 extern "C" int rex_eplog_step(rex_t* h, const float* reward, const uint8_t* done, const uint8_t* truncated, void* stream) {
   REX_ENTER(h, "rex_eplog_step");
-  REX_EPLOG_ON(h, "rex_eplog_step");
+  REX_NEEDS(h, eplog_mem, "rex_eplog_step", "rex_eplog_enable");
   if (!reward || !done) return set_err(REX_ERR_ARG, "rex_eplog_step: reward and done are required");
   eplog::Params p = h->eplog;
   p.reward = reward; p.done = done; p.truncated = truncated;
@@ -1201,13 +1201,13 @@ extern "C" int rex_eplog_step(rex_t* h, const float* reward, const uint8_t* done
 
 extern "C" int rex_eplog_sync(rex_t* h, const uint8_t* mask, int restart, void* stream) {
   REX_ENTER(h, "rex_eplog_sync");
-  REX_EPLOG_ON(h, "rex_eplog_sync");
+  REX_NEEDS(h, eplog_mem, "rex_eplog_sync", "rex_eplog_enable");
   return launch_eplog_sync(h, mask, restart, (hipStream_t)stream);
 }
 
 extern "C" int rex_eplog_read(rex_t* h, int64_t* out, int clear) {
   REX_ENTER(h, "rex_eplog_read");
-  REX_EPLOG_ON(h, "rex_eplog_read");
+  REX_NEEDS(h, eplog_mem, "rex_eplog_read", "rex_eplog_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_eplog_read: null argument");
   long long w[eplog::N_WORDS], o[4];
   HIP_TRY(hipDeviceSynchronize());
@@ -1221,33 +1221,28 @@ extern "C" int rex_eplog_read(rex_t* h, int64_t* out, int clear) {
   return REX_OK;
 }
 
+static int move_eplog_lane_state(rex_env* h, bool get, double* ep_return, int32_t* ep_len, float* shadow_task, hipStream_t st) {
+  const eplog::Lanes& ls = h->eplog.lanes;
+  if (int rc = move_lanes(get, ls.ep_return, ep_return, h->B, st)) return rc;
+  if (int rc = move_lanes(get, ls.ep_len, ep_len, h->B, st)) return rc;
+  return move_lanes(get, ls.shadow, shadow_task, h->B * h->dims.task_dim, st);
+}
 extern "C" int rex_eplog_get_lane_state(rex_t* h, double* ep_return, int32_t* ep_len, float* shadow_task, void* stream) {
   REX_ENTER(h, "rex_eplog_get_lane_state");
-  REX_EPLOG_ON(h, "rex_eplog_get_lane_state");
+  REX_NEEDS(h, eplog_mem, "rex_eplog_get_lane_state", "rex_eplog_enable");
   if (!ep_return || !ep_len || !shadow_task) return set_err(REX_ERR_ARG, "rex_eplog_get_lane_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(ep_return, h->eplog.lanes.ep_return, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ep_len, h->eplog.lanes.ep_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(shadow_task, h->eplog.lanes.shadow, sizeof(float) * B * (size_t)h->dims.task_dim, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_eplog_lane_state(h, true, ep_return, ep_len, shadow_task, (hipStream_t)stream);
 }
 extern "C" int rex_eplog_set_lane_state(rex_t* h, const double* ep_return, const int32_t* ep_len, const float* shadow_task, void* stream) {
   REX_ENTER(h, "rex_eplog_set_lane_state");
-  REX_EPLOG_ON(h, "rex_eplog_set_lane_state");
+  REX_NEEDS(h, eplog_mem, "rex_eplog_set_lane_state", "rex_eplog_enable");
   if (!ep_return || !ep_len || !shadow_task) return set_err(REX_ERR_ARG, "rex_eplog_set_lane_state: null argument");
-  hipStream_t st = (hipStream_t)stream; const size_t B = (size_t)h->B;
-  HIP_TRY(hipMemcpyAsync(h->eplog.lanes.ep_return, ep_return, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->eplog.lanes.ep_len, ep_len, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->eplog.lanes.shadow, shadow_task, sizeof(float) * B * (size_t)h->dims.task_dim, hipMemcpyDeviceToDevice, st));
-  return REX_OK;
+  return move_eplog_lane_state(h, false, const_cast<double*>(ep_return), const_cast<int32_t*>(ep_len), const_cast<float*>(shadow_task), (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------
 // off-policy replay buffer (replay_buffer.hpp): fused transposing add and on-device sampling over caller-owned transition-major buffers
 // ------------------------------------------------------------------------------------------
-#define REX_RBUF_ON(h, fn) \
-  do { if (!(h)->rbuf_mem) return set_err(REX_ERR_STATE, fn ": rex_rbuf_enable has not been called on this handle"); } while (0)
-
 extern "C" int rex_rbuf_enable(rex_t* h) {
   REX_ENTER(h, "rex_rbuf_enable");
   if (!h->rbuf_mem) HIP_TRY(hipMalloc(&h->rbuf_mem, sizeof(unsigned long long)));
@@ -1270,7 +1265,7 @@ static int rbuf_buf(const rex_env* h, const rex_rbuf_buffers* b, const char* fn,
 extern "C" int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, const float* obs, const void* action, const float* reward,
                             const uint8_t* done, const float* next_obs, const float* terminal_obs, const uint8_t* truncated, void* stream) {
   REX_ENTER(h, "rex_rbuf_add");
-  REX_RBUF_ON(h, "rex_rbuf_add");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_add", "rex_rbuf_enable");
   rbuf::AddParams p{};
   if (int rc = rbuf_buf(h, buf, "rex_rbuf_add", &p.buf)) return rc;
   if (t < 0 || t >= buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_add: slot %lld outside [0, %lld)", (long long)t, (long long)buf->T);
@@ -1278,7 +1273,7 @@ extern "C" int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, co
   p.src = rbuf::AddSrc{(const uint32_t*)obs, (const uint32_t*)action, reward, done, (const uint32_t*)next_obs, (const uint32_t*)terminal_obs, truncated};
   p.slot = t;
   const long long tiles = rbuf::add_tiles(h->B);
-  if (tiles > 0x7fffffffLL) return set_err(REX_ERR_ARG, "rex_rbuf_add: batch %lld is more than one launch takes", h->B);
+  if (!grid_fits(tiles)) return set_err(REX_ERR_ARG, "rex_rbuf_add: batch %lld is more than one launch takes", h->B);
   const unsigned groups = (unsigned)rbuf::add_groups(p.buf.obs_dim, p.buf.act_dim);
   hipLaunchKernelGGL(rbuf::rb_add_kernel, dim3((unsigned)tiles, groups), dim3(rbuf::BLOCK), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
@@ -1294,11 +1289,11 @@ static int launch_rbuf_sample(const rex_env* h, const char* fn, rbuf::SamplePara
   }
   if (p.n == 0) return REX_OK;
   const long long blocks = rbuf::sample_blocks(p.n);
-  if (blocks > 0x7fffffffLL) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
+  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
   // 16-byte accesses: with dim a multiple of 4 every row of a 16-byte aligned buffer starts 16-byte aligned
   const rbuf::Buf& b = p.buf;
-  p.vec_obs = (b.obs_dim % 4 == 0 && aligned16(b.obs) && aligned16(b.next_obs) && aligned16(p.out.obs) && aligned16(p.out.next_obs)) ? 1 : 0;
-  p.vec_act = (b.act_dim % 4 == 0 && aligned16(b.action) && aligned16(p.out.action)) ? 1 : 0;
+  p.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, p.out.obs, p.out.next_obs)) ? 1 : 0;
+  p.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, p.out.action)) ? 1 : 0;
   p.bad = (unsigned long long*)h->rbuf_mem;
   hipLaunchKernelGGL(rbuf::rb_sample_kernel, dim3((unsigned)blocks), dim3(rbuf::BLOCK), 0, st, p);
   HIP_TRY(hipGetLastError());
@@ -1309,7 +1304,7 @@ extern "C" int rex_rbuf_sample(rex_t* h, const rex_rbuf_buffers* buf, int64_t si
                                float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out, int64_t* index_out,
                                void* stream) {
   REX_ENTER(h, "rex_rbuf_sample");
-  REX_RBUF_ON(h, "rex_rbuf_sample");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_sample", "rex_rbuf_enable");
   rbuf::SampleParams p{};
   if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample", &p.buf)) return rc;
   if (size < 1 || size > buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_sample: size %lld outside [1, %lld]", (long long)size, (long long)buf->T);
@@ -1322,7 +1317,7 @@ extern "C" int rex_rbuf_sample(rex_t* h, const rex_rbuf_buffers* buf, int64_t si
 extern "C" int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int normalise, float* obs_out,
                                float* next_obs_out, void* action_out, float* reward_out, float* done_out, void* stream) {
   REX_ENTER(h, "rex_rbuf_gather");
-  REX_RBUF_ON(h, "rex_rbuf_gather");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_gather", "rex_rbuf_enable");
   rbuf::SampleParams p{};
   if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather", &p.buf)) return rc;
   if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rbuf_gather: n must be >= 0 and index given");
@@ -1333,12 +1328,7 @@ extern "C" int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int6
 
 extern "C" int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear) {
   REX_ENTER(h, "rex_rbuf_read_bad_indices");
-  REX_RBUF_ON(h, "rex_rbuf_read_bad_indices");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_read_bad_indices", "rex_rbuf_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_rbuf_read_bad_indices: null argument");
-  unsigned long long v = 0;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(&v, h->rbuf_mem, sizeof v, hipMemcpyDeviceToHost));
-  *out = (int64_t)v;
-  if (clear) HIP_TRY(hipMemset(h->rbuf_mem, 0, sizeof v));
-  return REX_OK;
+  return read_counter((unsigned long long*)h->rbuf_mem, out, clear);
 }

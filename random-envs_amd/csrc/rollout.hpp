@@ -4,43 +4,40 @@
 // for caller-owned SoA device buffers: obs [T][obs_dim][B], action [T][act_dim][B], everything else [T][B].
 //
 //   ro_add_kernel      one launch per step on the grid (chunks, rows): every row of the step (obs_dim + act_dim words rows, reward, value,
-//                      log_prob, done) is copied into slot t with the chunking of vecnorm.hpp; the reward row adds gamma * V(terminal_obs)
+//                      log_prob, done) is copied into slot t with the chunking of postpass.hpp; the reward row adds gamma * V(terminal_obs)
 //                      on the truncated lanes.
 //   ro_gae_kernel      one thread per env, serial in t from T-1 down.  The loads of a step do not depend on the recurrence, so a lane keeps
 //                      two groups of GAE_DEPTH time steps in registers: the loads of the next group are issued before the dependent fp64
 //                      chain of the current one runs.
-//   ro_moments_kernel  (n, mean, M2) of the flat advantage buffer: accumulate / to_partial / block_sum of vecnorm.hpp, one partial per block,
+//   ro_moments_kernel  (n, mean, M2) of the flat advantage buffer: accumulate / to_partial of vecnorm.hpp, block_sum of postpass.hpp, one partial per block,
 //   ro_finish_kernel   merged in a fixed order (runs of MERGE_GROUP partials in index order, then the runs pairwise over neighbours: a tree whose
 //                      shape depends on the partial count only); optionally rewrites the advantages as (A - mean) / (std + 1e-8) with the
 //                      unbiased deviation.
-//   ro_gather_kernel   a block takes G_SAMPLES sample ids and one group of G_ROWS rows, reads them from the SoA buffers (lane = sample, so
-//                      a run of consecutive ids is one coalesced read), stages them in LDS and writes the row-major [n][dim] outputs with
-//                      consecutive lanes on consecutive words.
+//   ro_gather_kernel   a block takes TILE_ITEMS sample ids and one group of TILE_ROWS rows, reads them from the SoA buffers (lane = sample, so
+//                      a run of consecutive ids is one coalesced read), stages them in postpass.hpp's LDS tile and writes the row-major
+//                      [n][dim] outputs with consecutive lanes on consecutive words.
 // No float atomics, no grid-wide sync, no host state between launches; the block counts depend on the sizes only.
 //
 // The arithmetic -- the bootstrap, the GAE step and the lane loop around it, the moments, the merge order, the normalisation, the gather's
-// index split, guard and tile addressing -- is __host__ __device__: tests/host_harness/rollout_host.cpp drives it with g++ in grid order.
+// index split and the staging of a row group -- is __host__ __device__: tests/host_harness/rollout_host.cpp drives it with g++ in grid order.
 #pragma once
-#include "vecnorm.hpp"
+#include "postpass.hpp"
+#include "vecnorm.hpp"   // the advantage moments: Mom, Part, accumulate, merge
 
 namespace rollout {
 
-using vecnorm::BLOCK;
-using vecnorm::VEC;
-using vecnorm::TILE;
-using vecnorm::F4;
-using vecnorm::Mom;
-using vecnorm::Part;
+using postpass::BLOCK, postpass::VEC, postpass::TILE, postpass::F4, postpass::U4, postpass::for_thread_groups;
+using postpass::TILE_ITEMS, postpass::TILE_ROWS, postpass::row_groups, postpass::tile_elem;
+using vecnorm::Mom, vecnorm::Part;
 
 constexpr int MAX_PARTS = 1024;       // partials of the statistics pass: the size of the scratch, independent of T
 constexpr int MERGE_GROUP = 4;        // partials one thread of the finish launch merges serially before the tree over the threads' results
 constexpr int GAE_BLOCK = 64;         // one wave per block: 32 768 envs spread over 512 SIMDs
 constexpr int GAE_DEPTH = 8;          // time steps per register group; two groups are live
-constexpr int G_SAMPLES = 64;         // samples per block of the gather: lane = sample
-constexpr int G_ROWS = 64;            // rows staged in LDS at a time
-constexpr int G_STRIDE = G_ROWS + 1;  // odd stride: lane l of a wave writes bank (l + row) % 64
-
-struct alignas(16) U4 { uint32_t x, y, z, w; };
+// postpass.hpp's tile under the names this header had before it (harness sources written against those still build; nothing here uses them)
+constexpr int G_SAMPLES = TILE_ITEMS, G_ROWS = TILE_ROWS, G_STRIDE = postpass::TILE_STRIDE;
+VN_HD inline int lds_slot(int sample, int row) { return postpass::tile_slot(sample, row); }
+VN_HD inline int tile_samples(long long n, long long block) { return postpass::tile_items(n, block); }
 
 // The caller's buffers (rex_rollout_buffers of include/rex.h) with the handle's sizes beside them.  action is copied as 4-byte words.
 struct Buf {
@@ -61,44 +58,23 @@ VN_HD inline float bootstrap_reward(float reward, float terminal_value, double g
 
 VN_HD inline int add_rows(int obs_dim, int act_dim) { return obs_dim + act_dim + 4; }   // + reward, value, log_prob, done
 
-// Thread t's share of copying one row of 4-byte words: its VEC consecutive words of every tile of the chunk.
-VN_HD inline void thread_copy_words(const uint32_t* src, uint32_t* dst, long long B, int chunk, long long tpc, int t, bool vec_ok) {
-  const long long tiles = (B + TILE - 1) / TILE;
-  long long t1 = (chunk + 1) * tpc; if (t1 > tiles) t1 = tiles;
-  for (long long tile = chunk * tpc; tile < t1; tile++) {
-    const long long i = vecnorm::elem_of(tile, t);
-    if (i >= B) break;
+// Thread t's share of copying one row of E elements: its VEC consecutive elements of every tile of the chunk, as one V where the wide path
+// is allowed (4-byte words: E = uint32_t, V = U4; the done row's bytes: E = uint8_t, V = uint32_t)
+template <class V, class E>
+VN_HD inline void thread_copy(const E* src, E* dst, long long B, int chunk, long long tpc, int t, bool vec_ok) {
+  for_thread_groups(B, chunk, tpc, t, [&](long long i) {
     if (vec_ok && i + VEC <= B) {
-      *reinterpret_cast<U4*>(dst + i) = *reinterpret_cast<const U4*>(src + i);
+      *reinterpret_cast<V*>(dst + i) = *reinterpret_cast<const V*>(src + i);
     } else {
       for (int k = 0; k < VEC && i + k < B; k++) dst[i + k] = src[i + k];
     }
-  }
-}
-
-// ... of the done row (bytes; one 4-byte access where the words path is allowed)
-VN_HD inline void thread_copy_bytes(const uint8_t* src, uint8_t* dst, long long B, int chunk, long long tpc, int t, bool vec_ok) {
-  const long long tiles = (B + TILE - 1) / TILE;
-  long long t1 = (chunk + 1) * tpc; if (t1 > tiles) t1 = tiles;
-  for (long long tile = chunk * tpc; tile < t1; tile++) {
-    const long long i = vecnorm::elem_of(tile, t);
-    if (i >= B) break;
-    if (vec_ok && i + VEC <= B) {
-      *reinterpret_cast<uint32_t*>(dst + i) = *reinterpret_cast<const uint32_t*>(src + i);
-    } else {
-      for (int k = 0; k < VEC && i + k < B; k++) dst[i + k] = src[i + k];
-    }
-  }
+  });
 }
 
 // ... of the reward row: the truncated lanes take the bootstrap (truncated == nullptr: a plain copy)
 VN_HD inline void thread_add_reward(const float* reward, const uint8_t* truncated, const float* terminal_value, float* dst, double gamma, long long B,
                                     int chunk, long long tpc, int t, bool vec_ok) {
-  const long long tiles = (B + TILE - 1) / TILE;
-  long long t1 = (chunk + 1) * tpc; if (t1 > tiles) t1 = tiles;
-  for (long long tile = chunk * tpc; tile < t1; tile++) {
-    const long long i = vecnorm::elem_of(tile, t);
-    if (i >= B) break;
+  for_thread_groups(B, chunk, tpc, t, [&](long long i) {
     if (vec_ok && i + VEC <= B) {
       F4 r = *reinterpret_cast<const F4*>(reward + i);
       if (truncated) {
@@ -118,7 +94,7 @@ VN_HD inline void thread_add_reward(const float* reward, const uint8_t* truncate
         dst[i + k] = (truncated && truncated[i + k]) ? bootstrap_reward(r, terminal_value[i + k], gamma) : r;
       }
     }
-  }
+  });
 }
 
 // The inputs of one rex_rollout_add
@@ -133,18 +109,18 @@ VN_HD inline void thread_add(const Buf& b, const AddSrc& s, long long slot, doub
   const int D = b.obs_dim, A = b.act_dim;
   const size_t o = (size_t)slot * B;
   if (row < D) {
-    thread_copy_words(reinterpret_cast<const uint32_t*>(s.obs) + (size_t)row * B, reinterpret_cast<uint32_t*>(b.obs) + (o * D + (size_t)row * B), B, chunk, tpc, t, vec_ok);
+    thread_copy<U4>(reinterpret_cast<const uint32_t*>(s.obs) + (size_t)row * B, reinterpret_cast<uint32_t*>(b.obs) + (o * D + (size_t)row * B), B, chunk, tpc, t, vec_ok);
   } else if (row < D + A) {
     const int r = row - D;
-    thread_copy_words(s.action + (size_t)r * B, b.action + (o * A + (size_t)r * B), B, chunk, tpc, t, vec_ok);
+    thread_copy<U4>(s.action + (size_t)r * B, b.action + (o * A + (size_t)r * B), B, chunk, tpc, t, vec_ok);
   } else if (row == D + A) {
     thread_add_reward(s.reward, s.truncated, s.terminal_value, b.reward + o, gamma, B, chunk, tpc, t, vec_ok);
   } else if (row == D + A + 1) {
-    thread_copy_words(reinterpret_cast<const uint32_t*>(s.value), reinterpret_cast<uint32_t*>(b.value) + o, B, chunk, tpc, t, vec_ok);
+    thread_copy<U4>(reinterpret_cast<const uint32_t*>(s.value), reinterpret_cast<uint32_t*>(b.value) + o, B, chunk, tpc, t, vec_ok);
   } else if (row == D + A + 2) {
-    thread_copy_words(reinterpret_cast<const uint32_t*>(s.log_prob), reinterpret_cast<uint32_t*>(b.log_prob) + o, B, chunk, tpc, t, vec_ok);
+    thread_copy<U4>(reinterpret_cast<const uint32_t*>(s.log_prob), reinterpret_cast<uint32_t*>(b.log_prob) + o, B, chunk, tpc, t, vec_ok);
   } else {
-    thread_copy_bytes(s.done, b.done + o, B, chunk, tpc, t, vec_ok);
+    thread_copy<uint32_t>(s.done, b.done + o, B, chunk, tpc, t, vec_ok);
   }
 }
 
@@ -244,11 +220,7 @@ VN_HD inline float adv_normalise(float a, double mean, double denom) { return (f
 
 // Thread t's share of normalising the flat buffer in place
 VN_HD inline void thread_normalise_adv(float* x, long long N, int chunk, long long tpc, int t, double mean, double denom, bool vec_ok) {
-  const long long tiles = (N + TILE - 1) / TILE;
-  long long t1 = (chunk + 1) * tpc; if (t1 > tiles) t1 = tiles;
-  for (long long tile = chunk * tpc; tile < t1; tile++) {
-    const long long i = vecnorm::elem_of(tile, t);
-    if (i >= N) break;
+  for_thread_groups(N, chunk, tpc, t, [&](long long i) {
     if (vec_ok && i + VEC <= N) {
       F4 q = *reinterpret_cast<const F4*>(x + i);
       q.x = adv_normalise(q.x, mean, denom); q.y = adv_normalise(q.y, mean, denom);
@@ -257,25 +229,25 @@ VN_HD inline void thread_normalise_adv(float* x, long long N, int chunk, long lo
     } else {
       for (int k = 0; k < VEC && i + k < N; k++) x[i + k] = adv_normalise(x[i + k], mean, denom);
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------ gather
-// flat sample id s = t * B + b.  An id outside [0, T * B) is not ok and is never turned into an address.
+// flat sample id s = t * B + b, behind postpass::guard_id: an id outside [0, T * B) is not ok and is never turned into an address.
 struct Sample { long long t, b; bool ok; };
 VN_HD inline Sample split_index(long long s, long long T, long long B) {
+  const postpass::Id id = postpass::guard_id(s, T, B);
   Sample o;
-  o.ok = s >= 0 && s < T * B;
-  const long long ss = o.ok ? s : 0;
-  o.t = ss / B; o.b = ss - o.t * B;
+  o.ok = id.ok;
+  o.t = id.s / B; o.b = id.s - o.t * B;
   return o;
 }
 VN_HD inline size_t soa_offset(const Sample& s, int dim, int row, long long B) { return ((size_t)s.t * dim + row) * (size_t)B + (size_t)s.b; }
-VN_HD inline int lds_slot(int sample, int row) { return sample * G_STRIDE + row; }
-VN_HD inline int tile_samples(long long n, long long block) { const long long left = n - block * G_SAMPLES; return left < G_SAMPLES ? (int)left : G_SAMPLES; }
-VN_HD inline int row_groups(int dim) { return (dim + G_ROWS - 1) / G_ROWS; }
-// word e of a staged group of `nr` rows: which sample, which row
-VN_HD inline void tile_elem(int e, int nr, int* sample, int* row) { *sample = e / nr; *row = e - *sample * nr; }
+
+// Thread t's share of staging rows [r0, r0 + nr) of its lane's sample `sm` from src [T][dim][B] (zeros for an id out of range) ...
+VN_HD inline void thread_gather_stage(const uint32_t* src, int dim, int r0, int nr, const Sample& sm, long long B, int t, uint32_t* lds) {
+  postpass::tile_stage(lds, nr, t, [&](int rr) { return sm.ok ? src[soa_offset(sm, dim, r0 + rr, B)] : 0u; });
+}
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ device side
@@ -305,7 +277,7 @@ __global__ __launch_bounds__(BLOCK) void ro_moments_kernel(StatParams p) {
   const double c = vecnorm::shift_for((double)p.adv[0], 0.0);
   const Mom m = vecnorm::thread_moments_obs(p.adv, nullptr, p.N, blockIdx.x, p.tpc, threadIdx.x, c, p.vec_ok);
   double v[4] = {m.n, m.s1, m.s2, m.seen};
-  vecnorm::block_sum<4>(v, sm);
+  postpass::block_sum<4>(v, sm);
   if (threadIdx.x == 0) p.scratch[blockIdx.x] = vecnorm::to_partial(Mom{v[0], v[1], v[2], v[3]}, c);
 }
 
@@ -330,28 +302,22 @@ struct GatherParams {
   unsigned long long* bad;   // ids outside [0, T * B) met so far
 };
 
-// rows [r0, r0 + G_ROWS) of the block's samples from src [T][dim][B] into out [n][dim]
+// rows [r0, r0 + TILE_ROWS) of the block's samples from src [T][dim][B] into out [n][dim]
 __device__ inline void gather_rows(const uint32_t* src, uint32_t* out, int dim, int r0, const Sample& sm, bool live, long long s0, int ns, long long B,
                                    uint32_t* lds) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nr = dim - r0 < G_ROWS ? dim - r0 : G_ROWS;
-  if (live)
-    for (int rr = wave; rr < nr; rr += BLOCK / 64) lds[lds_slot(lane, rr)] = sm.ok ? src[soa_offset(sm, dim, r0 + rr, B)] : 0u;
+  const int nr = dim - r0 < TILE_ROWS ? dim - r0 : TILE_ROWS;   // (not postpass::group_rows: through the call the kernel compiles to other code)
+  if (live) thread_gather_stage(src, dim, r0, nr, sm, B, threadIdx.x, lds);
   __syncthreads();
-  for (int e = threadIdx.x; e < ns * nr; e += BLOCK) {
-    int s, rr;
-    tile_elem(e, nr, &s, &rr);
-    out[(size_t)(s0 + s) * dim + r0 + rr] = lds[lds_slot(s, rr)];
-  }
+  postpass::tile_write(out, dim, r0, nr, (size_t)s0, ns, threadIdx.x, lds);
 }
 
-// grid (tiles of G_SAMPLES samples, row groups): the groups of the observation rows, then those of the action rows; the blocks of group 0
+// grid (tiles of TILE_ITEMS samples, row groups): the groups of the observation rows, then those of the action rows; the blocks of group 0
 // also write the [n] outputs and count the ids out of range
 __global__ __launch_bounds__(BLOCK) void ro_gather_kernel(GatherParams p) {
-  __shared__ uint32_t lds[G_SAMPLES * G_STRIDE];
+  __shared__ uint32_t lds[postpass::TILE_WORDS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long s0 = (long long)blockIdx.x * G_SAMPLES;
-  const int ns = tile_samples(p.n, blockIdx.x);
+  const long long s0 = (long long)blockIdx.x * TILE_ITEMS;
+  const int ns = postpass::tile_items(p.n, blockIdx.x);
   const bool live = lane < ns;
   const Sample sm = split_index(live ? p.index[s0 + lane] : 0, p.buf.T, p.buf.B);
   if (blockIdx.y == 0 && live) {   // one [n] output per wave
@@ -363,9 +329,9 @@ __global__ __launch_bounds__(BLOCK) void ro_gather_kernel(GatherParams p) {
   }
   const int obs_groups = row_groups(p.buf.obs_dim), g = blockIdx.y;
   if (g < obs_groups) {
-    if (p.obs_out) gather_rows(reinterpret_cast<const uint32_t*>(p.buf.obs), p.obs_out, p.buf.obs_dim, g * G_ROWS, sm, live, s0, ns, p.buf.B, lds);
+    if (p.obs_out) gather_rows(reinterpret_cast<const uint32_t*>(p.buf.obs), p.obs_out, p.buf.obs_dim, g * TILE_ROWS, sm, live, s0, ns, p.buf.B, lds);
   } else if (p.action_out) {
-    gather_rows(p.buf.action, p.action_out, p.buf.act_dim, (g - obs_groups) * G_ROWS, sm, live, s0, ns, p.buf.B, lds);
+    gather_rows(p.buf.action, p.action_out, p.buf.act_dim, (g - obs_groups) * TILE_ROWS, sm, live, s0, ns, p.buf.B, lds);
   }
 }
 #endif  // __HIPCC__

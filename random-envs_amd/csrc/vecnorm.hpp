@@ -17,40 +17,22 @@
 // then leaves S2 - S1^2/n ~ n m^2 2^-53 of cancellation noise in an M2 whose true value is the 1e-4 prior -- 1e-8 to 1e-6
 // relative, depending on the summation order.  With an element of the batch as the shift the noise is (mean - c)^2 / var ulps, i.e. O(1) ulp.
 //
-// The per-thread accumulation, the partial merge, the running update and the normalisation are __host__ __device__:
+// The block, its chunking (chunk_count, tiles_per_chunk, elem_of) and block_sum are postpass.hpp's; the five walks below keep the loop of
+// postpass::for_thread_groups written out, because as lambdas the two kernels compile to other code (profiles/HISTORY.md).  The per-thread
+// accumulation, the partial merge, the running update and the normalisation are __host__ __device__:
 // tests/host_harness/vecnorm_host.cpp instantiates them with g++ and emulates the grid / chunk / reduction order on the CPU.
 #pragma once
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define VN_HD __host__ __device__
-#else
-#define VN_HD
-#endif
+#include "postpass.hpp"
 
 namespace vecnorm {
 
-constexpr int BLOCK = 256;            // threads per block (four waves)
-constexpr int VEC = 4;                // elements per thread and tile: one 16-byte load
-constexpr int TILE = BLOCK * VEC;     // elements a block covers per iteration
-constexpr int MAX_CHUNKS = 64;        // partials a block of the normalise pass merges serially
-constexpr int GRID_CAP = 4096;        // blocks per launch past which chunks grow (grid-stride) instead of multiplying
+using postpass::BLOCK, postpass::VEC, postpass::TILE, postpass::F4;
+using postpass::chunk_count, postpass::tiles_per_chunk, postpass::elem_of;   // (harness sources written before postpass.hpp say vecnorm::)
 
-// blocks per row: a function of (B, rows) only
-VN_HD inline int chunk_count(long long B, int rows) {
-  const long long tiles = (B + TILE - 1) / TILE;
-  int cap = GRID_CAP / rows;
-  cap = cap > MAX_CHUNKS ? MAX_CHUNKS : (cap < 1 ? 1 : cap);
-  return tiles < cap ? (int)tiles : cap;
-}
-VN_HD inline long long tiles_per_chunk(long long B, int chunks) {
-  const long long tiles = (B + TILE - 1) / TILE;
-  return (tiles + chunks - 1) / chunks;
-}
-
-struct alignas(16) F4 { float x, y, z, w; };   // one 16-byte load / store
 struct Mom { double n, s1, s2, seen; };            // per-thread sums about the shift c; seen counts the non-finite elements too
 struct Part { double n, mean, m2, seen; };         // one block's (or a row's merged) batch moments
 struct Stat { double count, mean, var; };
@@ -120,9 +102,6 @@ VN_HD inline double ret_update(double ret, double gamma, float reward) {
 }
 
 VN_HD inline double shift_for(double first, double running_mean) { return is_finite(first) ? first : running_mean; }
-
-// first element of thread t's group in `tile`
-VN_HD inline long long elem_of(long long tile, int t) { return (tile * BLOCK + t) * VEC; }
 
 // What thread t of block `chunk` sums of one observation row x[0..B): its VEC consecutive elements of every tile of the chunk.
 VN_HD inline Mom thread_moments_obs(const float* x, const uint8_t* mask, long long B, int chunk, long long tpc, int t, double c, bool vec_ok) {
@@ -269,23 +248,6 @@ struct Params {
   LaneState lanes;
 };
 
-// Fixed-order block sum of K doubles per thread: butterfly inside each wave, then the four waves in index order.  Thread 0 holds the result.
-template <int K>
-__device__ inline void block_sum(double (&v)[K], double* sm /*[K][BLOCK / 64]*/) {
-  for (int off = 32; off; off >>= 1)
-    for (int k = 0; k < K; k++) v[k] += __shfl_down(v[k], off, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < K; k++) sm[k * (BLOCK / 64) + wave] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int k = 0; k < K; k++) {
-      double s = sm[k * (BLOCK / 64)];
-      for (int w = 1; w < BLOCK / 64; w++) s += sm[k * (BLOCK / 64) + w];
-      v[k] = s;
-    }
-}
-
 __global__ __launch_bounds__(BLOCK) void vn_moments_kernel(Params p) {
   __shared__ double sm[7 * (BLOCK / 64)];
   const int chunk = blockIdx.x, row = p.row0 + blockIdx.y, t = threadIdx.x;
@@ -297,14 +259,14 @@ __global__ __launch_bounds__(BLOCK) void vn_moments_kernel(Params p) {
     const double c = shift_for((double)x[0], running_mean);
     const Mom m = thread_moments_obs(x, p.mask, p.B, chunk, p.tpc, t, c, p.vec_ok);
     double v[4] = {m.n, m.s1, m.s2, m.seen};
-    block_sum<4>(v, sm);
+    postpass::block_sum<4>(v, sm);
     if (t == 0) p.parts[(size_t)row * p.chunks + chunk] = to_partial(Mom{v[0], v[1], v[2], v[3]}, c);
   } else {
     const double c = shift_for(ret_update(p.lanes.ret[0], p.gamma, p.reward_in[0]), running_mean);
     double agg[3] = {0, 0, 0};
     const Mom m = thread_return_row(p.lanes, p.reward_in, p.done, p.ep_return_out, p.ep_len_out, p.B, chunk, p.tpc, t, c, p.gamma, p.upd_ret, agg);
     double v[7] = {m.n, m.s1, m.s2, m.seen, agg[0], agg[1], agg[2]};
-    block_sum<7>(v, sm);
+    postpass::block_sum<7>(v, sm);
     if (t == 0) {
       p.parts[(size_t)row * p.chunks + chunk] = to_partial(Mom{v[0], v[1], v[2], v[3]}, c);
       for (int k = 0; k < 3; k++) p.agg_parts[chunk * 3 + k] = v[4 + k];

@@ -12,11 +12,12 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._layer import Layer
 
 FIELDS = ("task", "episode_return", "episode_length", "truncated", "env", "step")
 
 
-class EpisodeLog:
+class EpisodeLog(Layer):
     """``EpisodeLog(env, capacity)`` over a :class:`VecRandomEnv` or a :class:`NormalizedVecRandomEnv` (it always reads the RAW
     reward buffer of the wrapped env).  Call order per step: ``env.step`` -> ``log.record()``; after anything that changes the
     task or restarts lanes from outside (``reset``, ``set_task``, ``set_random_task``, ``set_state``, ``set_full_state``):
@@ -31,15 +32,12 @@ class EpisodeLog:
 
     def __init__(self, env, capacity):
         import torch
-        self._torch = torch
-        self.env = env
-        base = getattr(env, "env", env)            # the wrapped env of a NormalizedVecRandomEnv
-        self._base = base
-        self._L, self._h = base._L, base._h
+        super().__init__(env)
+        base = self._base
         self.capacity = int(capacity)
         if self.capacity <= 0:
             raise ValueError("EpisodeLog: capacity must be > 0")
-        self.batch, self.device, self.task_dim = base.batch, base.device, int(base.task_dim)
+        self.task_dim = int(base.task_dim)
         N, dev = self.capacity, self.device
         self.task = torch.zeros(self.task_dim, N, dtype=torch.float32, device=dev)
         self.ep_return = torch.zeros(N, dtype=torch.float64, device=dev)
@@ -55,14 +53,6 @@ class EpisodeLog:
     def _mine(self):
         if getattr(self._base, "_episode_log", None) is not self:
             raise RuntimeError("EpisodeLog: another EpisodeLog was made over this env and owns its ledger now (one log per env)")
-
-    # ------------------------------------------------------------------ plumbing
-    @staticmethod
-    def _p(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-    def _stream(self):
-        return self._base._stream()
 
     # ------------------------------------------------------------------ per step
     def record(self, truncated=False):

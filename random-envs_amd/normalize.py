@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._layer import _p
 
 PRIOR_COUNT = 1e-4      # RunningMeanStd's initial pseudo-count (mean 0, var 1)
 
@@ -114,9 +115,7 @@ class NormalizedVecRandomEnv:
         _native.check(self._L.rex_norm_set_training(self._h, int(self._training)))
 
     # ------------------------------------------------------------------ gym protocol
-    @staticmethod
-    def _p(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
+    _p = staticmethod(_p)
 
     def reset(self, mask=None):
         env = self.env

@@ -12,27 +12,23 @@ minibatch on the device (Philox4x32-10, no host randomness, no synchronisation) 
 import ctypes
 
 from . import _native
+from ._layer import Layer
 
 _FIELDS = ("obs", "next_obs", "action", "reward", "done", "timeout")
 
 
-class ReplayBuffer:
+class ReplayBuffer(Layer):
     """``ReplayBuffer(env, n_slots, seed=0)`` over a :class:`VecRandomEnv` or a :class:`NormalizedVecRandomEnv`; it holds
     ``n_slots * env.batch`` transitions."""
 
     def __init__(self, env, n_slots, seed=0):
         import torch
-        self._torch = torch
-        self.env = env
-        base = getattr(env, "env", env)            # the wrapped env of a NormalizedVecRandomEnv
-        self._base = base
+        super().__init__(env)
+        base = self._base
         self._normalized = base is not env
-        self._L, self._h = base._L, base._h
         self.n_slots, self.seed = int(n_slots), int(seed) & 0xFFFFFFFFFFFFFFFF
         if self.n_slots <= 0:
             raise ValueError("ReplayBuffer: n_slots must be > 0")
-        self.batch, self.device = base.batch, base.device
-        self.obs_dim, self.act_dim = int(base.dims.obs_dim), int(base.dims.act_dim)
         _native.check(self._L.rex_rbuf_enable(self._h))
         T, B = self.n_slots, self.batch
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -42,18 +38,6 @@ class ReplayBuffer:
         self.done, self.timeout = torch.zeros(T, B, dtype=torch.uint8, device=self.device), torch.zeros(T, B, dtype=torch.uint8, device=self.device)
         self._desc = _native.RexRbufBuffers(*[getattr(self, k).data_ptr() for k in _FIELDS], T)
         self.pos, self.full, self.draws = 0, False, 0
-
-    # ------------------------------------------------------------------ plumbing
-    @staticmethod
-    def _p(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-    def _stream(self):
-        return self._base._stream()
-
-    def _check(self, t, shape, dtypes, name):
-        if t.device != self.device or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous():
-            raise ValueError("ReplayBuffer: %s must be a contiguous %s tensor of %s on %s" % (name, list(shape), dtypes[0], self.device))
 
     def _normalise_flag(self, normalize):
         return int(self._normalized if normalize is None else bool(normalize))
@@ -118,9 +102,7 @@ class ReplayBuffer:
     def gather(self, index, normalize=None):
         """The same launch for the caller's ids ``index`` (int64 on the device): prioritised schemes, tests.  An id outside
         ``[0, n_slots * batch)`` gives zeros and is counted (:meth:`bad_indices`)."""
-        t = self._torch
-        if index.device != self.device or index.dtype != t.int64 or index.dim() != 1 or not index.is_contiguous():
-            raise ValueError("ReplayBuffer.gather: index must be a contiguous 1-d int64 tensor on %s" % self.device)
+        self._check_index(index)
         n = index.numel()
         out = self._outputs(n, False)
         _native.check(self._L.rex_rbuf_gather(self._h, ctypes.byref(self._desc), self._p(index), n, self._normalise_flag(normalize),
@@ -131,9 +113,7 @@ class ReplayBuffer:
 
     def bad_indices(self, clear=True):
         """Ids out of range the gathers met since the last clearing read (their outputs are zeros).  Synchronises."""
-        out = ctypes.c_int64()
-        _native.check(self._L.rex_rbuf_read_bad_indices(self._h, ctypes.byref(out), int(bool(clear))))
-        return int(out.value)
+        return self._read_counter(self._L.rex_rbuf_read_bad_indices, clear)
 
     # ------------------------------------------------------------------ state
     def state_dict(self):

@@ -9,23 +9,19 @@ csrc/rollout.hpp).
 import ctypes
 
 from . import _native
+from ._layer import Layer
 
 
-class RolloutBuffer:
+class RolloutBuffer(Layer):
     """``RolloutBuffer(env, n_steps)`` over a :class:`VecRandomEnv` or a :class:`NormalizedVecRandomEnv`."""
 
     def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95):
         import torch
-        self._torch = torch
-        self.env = env
-        base = getattr(env, "env", env)            # the wrapped env of a NormalizedVecRandomEnv
-        self._base = base
-        self._L, self._h = base._L, base._h
+        super().__init__(env)
+        base = self._base
         self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
         if self.n_steps <= 0:
             raise ValueError("RolloutBuffer: n_steps must be > 0")
-        self.batch, self.device = base.batch, base.device
-        self.obs_dim, self.act_dim = int(base.dims.obs_dim), int(base.dims.act_dim)
         _native.check(self._L.rex_rollout_enable(self._h))
         T, B = self.n_steps, self.batch
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -37,18 +33,6 @@ class RolloutBuffer:
         self._desc = _native.RexRolloutBuffers(*[t.data_ptr() for t in (self.obs, self.action, self.reward, self.value, self.log_prob,
                                                                         self.advantage, self.returns, self.done)], T)
         self.pos = 0
-
-    # ------------------------------------------------------------------ plumbing
-    @staticmethod
-    def _p(t):
-        return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-    def _stream(self):
-        return self._base._stream()
-
-    def _check(self, t, shape, dtypes, name):
-        if t.device != self.device or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous():
-            raise ValueError("RolloutBuffer: %s must be a contiguous %s tensor of %s on %s" % (name, list(shape), dtypes[0], self.device))
 
     @property
     def full(self):
@@ -103,17 +87,14 @@ class RolloutBuffer:
 
     def bad_indices(self, clear=True):
         """Sample ids outside [0, T * B) the gathers met since the last clearing read (their outputs are zeros).  Synchronises."""
-        out = ctypes.c_int64()
-        _native.check(self._L.rex_rollout_read_bad_indices(self._h, ctypes.byref(out), int(bool(clear))))
-        return int(out.value)
+        return self._read_counter(self._L.rex_rollout_read_bad_indices, clear)
 
     # ------------------------------------------------------------------ learn
     def gather(self, index):
         """One minibatch for the flat sample ids ``index`` (int64 on the device, ``s = t * B + b``) in one launch: a dict of
         ``obs`` [n, obs_dim], ``action`` [n, act_dim] (row-major) and ``advantage`` / ``returns`` / ``value`` / ``log_prob`` [n]."""
         t = self._torch
-        if index.device != self.device or index.dtype != t.int64 or index.dim() != 1 or not index.is_contiguous():
-            raise ValueError("RolloutBuffer.gather: index must be a contiguous 1-d int64 tensor on %s" % self.device)
+        self._check_index(index)
         n = index.numel()
         f32 = dict(dtype=t.float32, device=self.device)
         out = dict(obs=t.empty(n, self.obs_dim, **f32), action=t.empty(n, self.act_dim, dtype=self.action.dtype, device=self.device),

@@ -24,7 +24,6 @@ the machine.
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -34,6 +33,7 @@ TESTS = os.path.dirname(HERE)
 ROOT = os.path.dirname(TESTS)
 sys.path.insert(0, TESTS)
 sys.path.insert(0, ROOT)
+from host_harness.build import build_so  # noqa: E402
 
 KINDS = ("hopper", "halfcheetah", "walker2d")
 KIND_ID = {"hopper": 1, "halfcheetah": 2, "walker2d": 3}
@@ -53,18 +53,13 @@ N_ENVS, N_STEPS, EVERY = 32, 16, 4
 FREE = slice(10, 16)      # lanes that start 1 m up
 LYING = slice(16, 32)     # lanes that start pitched at low height
 PATH = os.path.join(HERE, "planar_decisions_bits.npz")
-SRC = os.path.join(TESTS, "host_harness", "decisions_host.cpp")
-SO = os.path.join(TESTS, "host_harness", "_build_decisions_host.so")
-DEPS = [SRC] + [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in ("planar_spec.hpp", "planar_engine.hpp", "planar_model.hpp", "probes.hpp")]
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        if (not os.path.exists(SO)) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", SO, SRC])
-        _lib = ctypes.CDLL(SO)
+        _lib = ctypes.CDLL(build_so("decisions_host", "decisions_host.cpp"))
     return _lib
 
 

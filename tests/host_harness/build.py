@@ -1,5 +1,6 @@
-"""Builds and binds the host instantiation of the kernel math (TEST HARNESS ONLY)."""
+"""Builds the host instantiations of the kernel math (build_so: every harness of this folder) and binds the planar one (TEST HARNESS ONLY)."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -7,26 +8,30 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SO = os.path.join(HERE, "_build_planar_host.so")
-SRC = os.path.join(HERE, "planar_host.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in
-                ("planar_spec.hpp", "planar_engine.hpp", "planar_model.hpp", "probes.hpp")]
 _D = ctypes.POINTER(ctypes.c_double)
 _lib = None
 KINDS = {"hopper": 1, "halfcheetah": 2, "walker2d": 3}
 
 
+def build_so(name, src, extra_flags=()):
+    """Path of _build_<name>.so: ``src`` (a file of this folder) compiled with g++ when the library is missing or older than the
+    source, ANY header of csrc/ or of this folder, or the C-ABI -- a hand-kept list of headers would let a test run a stale library."""
+    so = os.path.join(HERE, "_build_%s.so" % name)
+    src = os.path.join(HERE, src)
+    deps = [src, os.path.join(ROOT, "include", "rex.h")] + glob.glob(os.path.join(ROOT, "random-envs_amd", "csrc", "*.hpp")) + glob.glob(os.path.join(HERE, "*.hpp"))
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared"] + list(extra_flags) + ["-o", so, src])
+    return so
+
+
 def lib():
     global _lib
     if _lib is None:
-        stale = (not os.path.exists(SO)) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS)
-        if stale:
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", SO, SRC])
         try:
-            _lib = ctypes.CDLL(SO)
-        except OSError:
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", SO, SRC])
-            _lib = ctypes.CDLL(SO)
+            _lib = ctypes.CDLL(build_so("planar_host", "planar_host.cpp"))
+        except OSError:                               # a library another toolchain or a cut-off build left behind: build it again
+            os.remove(os.path.join(HERE, "_build_planar_host.so"))
+            _lib = ctypes.CDLL(build_so("planar_host", "planar_host.cpp"))
     return _lib
 
 

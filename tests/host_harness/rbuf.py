@@ -1,16 +1,11 @@
 """Builds and binds the host instantiation of the replay buffer kernels' math, rbuf_host.cpp (TEST HARNESS ONLY): numpy arrays in, the
 functions of csrc/replay_buffer.hpp driven block by block and thread by thread, numpy arrays out."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-SRC = os.path.join(HERE, "rbuf_host.cpp")
-SO = os.path.join(HERE, "_build_rbuf_host.so")
-DEPS = [SRC] + [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in ("replay_buffer.hpp", "vecnorm.hpp")]
+from .build import build_so
+
 FIELDS = ("obs", "next_obs", "action", "reward", "done", "timeout")
 _lib = None
 
@@ -19,9 +14,7 @@ def lib():
     """rbuf_host.cpp built with g++ (rebuilt when it or a header is newer); no fused multiply-add"""
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, SRC])
-        _lib = ctypes.CDLL(SO)
+        _lib = ctypes.CDLL(build_so("rbuf_host", "rbuf_host.cpp", ["-ffp-contract=off"]))
         vp, ll, u64, i32, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_double
         _lib.rb_host_philox.argtypes = [vp, vp, vp]
         _lib.rb_host_philox.restype = None

@@ -15,7 +15,6 @@ namespace {
 Buf make_buf(void** p, long long T, long long B, int obs_dim, int act_dim) {
   return Buf{(uint32_t*)p[0], (uint32_t*)p[1], (uint32_t*)p[2], (float*)p[3], (uint8_t*)p[4], (uint8_t*)p[5], T, B, obs_dim, act_dim};
 }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -35,7 +34,7 @@ extern "C" int rb_host_add(void** bufs, long long T, long long B, int obs_dim, i
   if (slot < 0 || slot >= T) return -1;
   const AddSrc s{(const uint32_t*)src[0], (const uint32_t*)src[1], (const float*)src[2], (const uint8_t*)src[3], (const uint32_t*)src[4],
                  (const uint32_t*)src[5], (const uint8_t*)src[6]};
-  std::vector<uint32_t> lds((size_t)A_ENVS * A_STRIDE);
+  std::vector<uint32_t> lds(postpass::TILE_WORDS);
   const int groups = add_groups(obs_dim, act_dim);
   for (int group = 0; group < groups; group++)           // blockIdx.y
     for (long long tile = 0; tile < add_tiles(B); tile++) {   // blockIdx.x
@@ -60,8 +59,8 @@ extern "C" int rb_host_sample(void** bufs, long long T, long long B, int obs_dim
   const Out o{(uint32_t*)outs[0], (uint32_t*)outs[1], (uint32_t*)outs[2], (float*)outs[3], (float*)outs[4], (long long*)outs[5]};
   const Norm nm{stats, obs_dim + 1, norm_obs, norm_reward, eps, clip_obs, clip_reward};
   const long long N = index ? T * B : size * B;
-  const bool vec_obs = !force_scalar && obs_dim % 4 == 0 && aligned16(b.obs) && aligned16(b.next_obs) && aligned16(o.obs) && aligned16(o.next_obs);
-  const bool vec_act = !force_scalar && act_dim % 4 == 0 && aligned16(b.action) && aligned16(o.action);
+  const bool vec_obs = !force_scalar && obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, o.obs, o.next_obs);
+  const bool vec_act = !force_scalar && act_dim % 4 == 0 && postpass::all_aligned16(b.action, o.action);
   const bool norm = nm.stats && nm.norm_obs;
   double s_mean[PASS_COLS], s_inv[PASS_COLS];
   for (long long blk = 0; blk < sample_blocks(n); blk++) {

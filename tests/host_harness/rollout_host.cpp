@@ -1,38 +1,15 @@
 // Host instantiation of the rollout kernels' math (TEST HARNESS ONLY): the __host__ __device__ functions of csrc/rollout.hpp compiled
 // with g++ -ffp-contract=off and driven in the order the launches run them -- every block of the grid, every thread of it, the wave
-// butterfly and four-wave sum of vecnorm.hpp's block_sum, the grouped merge and its tree, the LDS tile of the gather as an array -- so
+// butterfly and four-wave sum of postpass.hpp's block_sum, the grouped merge and its tree, the LDS tile of the gather as an array -- so
 // the CPU tests hold the kernels' arithmetic and addressing to the oracle for any size without a GPU.
-#include <cstring>
 #include <vector>
 
 #include "../../random-envs_amd/csrc/rollout.hpp"
+#include "block_sum_host.hpp"
 
 using namespace rollout;
 
 namespace {
-
-// block_sum of vecnorm.hpp: __shfl_down butterfly (a lane past the wave's end reads itself), then the waves in index order
-template <int K>
-void block_sum_host(const std::vector<double>& v /*[BLOCK][K]*/, double (&out)[K]) {
-  double wave_sum[BLOCK / 64][K];
-  for (int w = 0; w < BLOCK / 64; w++) {
-    double lane[64][K];
-    for (int l = 0; l < 64; l++)
-      for (int k = 0; k < K; k++) lane[l][k] = v[(size_t)(w * 64 + l) * K + k];
-    for (int off = 32; off; off >>= 1) {
-      double nxt[64][K];
-      for (int l = 0; l < 64; l++)
-        for (int k = 0; k < K; k++) nxt[l][k] = lane[l][k] + (l + off < 64 ? lane[l + off][k] : lane[l][k]);
-      memcpy(lane, nxt, sizeof lane);
-    }
-    for (int k = 0; k < K; k++) wave_sum[w][k] = lane[0][k];
-  }
-  for (int k = 0; k < K; k++) {
-    double s = wave_sum[0][k];
-    for (int w = 1; w < BLOCK / 64; w++) s += wave_sum[w][k];
-    out[k] = s;
-  }
-}
 
 Buf make_buf(void** p, long long T, long long B, int obs_dim, int act_dim) {
   return Buf{(float*)p[0], (uint32_t*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], (float*)p[5], (float*)p[6], (uint8_t*)p[7], T, B, obs_dim, act_dim};
@@ -42,6 +19,15 @@ Buf make_buf(void** p, long long T, long long B, int obs_dim, int act_dim) {
 
 extern "C" int ro_host_parts(long long N) { return part_count(N); }
 
+// One block's trip through postpass.hpp's LDS tile: n items by nr rows of src [nr][n] staged (lane = item), then written to rows
+// [r0, r0 + nr) of dst [n][dim].
+extern "C" void ro_host_tile(const uint32_t* src, int n, int nr, uint32_t* dst, int dim, int r0) {
+  std::vector<uint32_t> lds(postpass::TILE_WORDS);
+  for (int t = 0; t < BLOCK; t++)
+    if ((t & 63) < n) postpass::tile_stage(lds.data(), nr, t, [&](int rr) { return src[(size_t)rr * n + (t & 63)]; });
+  for (int t = 0; t < BLOCK; t++) postpass::tile_write(dst, dim, r0, nr, 0, n, t, lds.data());
+}
+
 // bufs: obs, action, reward, value, log_prob, advantage, returns, done.  src: obs, action, reward, done, value, log_prob, truncated, terminal_value.
 extern "C" int ro_host_add(void** bufs, long long T, long long B, int obs_dim, int act_dim, long long slot, void** src, double gamma, int vec_ok) {
   const Buf b = make_buf(bufs, T, B, obs_dim, act_dim);
@@ -49,8 +35,8 @@ extern "C" int ro_host_add(void** bufs, long long T, long long B, int obs_dim, i
                  (const uint8_t*)src[6], (const float*)src[7]};
   if (slot < 0 || slot >= T) return -1;
   const int rows = add_rows(obs_dim, act_dim);
-  const int chunks = vecnorm::chunk_count(B, rows);
-  const long long tpc = vecnorm::tiles_per_chunk(B, chunks);
+  const int chunks = postpass::chunk_count(B, rows);
+  const long long tpc = postpass::tiles_per_chunk(B, chunks);
   for (int row = 0; row < rows; row++)
     for (int chunk = 0; chunk < chunks; chunk++)
       for (int t = 0; t < BLOCK; t++) thread_add(b, s, slot, gamma, row, chunk, tpc, t, vec_ok != 0);
@@ -72,7 +58,7 @@ extern "C" int ro_host_gae(void** bufs, long long T, long long B, const float* l
 // out: n, mean, M2, non-finite elements
 extern "C" int ro_host_adv_stats(float* adv, long long N, int normalise, int vec_ok, double* out) {
   const int parts = part_count(N);
-  const long long tpc = vecnorm::tiles_per_chunk(N, parts);
+  const long long tpc = postpass::tiles_per_chunk(N, parts);
   std::vector<Part> scratch(parts);
   // ---- moments launch
   for (int blk = 0; blk < parts; blk++) {
@@ -104,12 +90,12 @@ extern "C" int ro_host_adv_stats(float* adv, long long N, int normalise, int vec
 extern "C" int ro_host_gather(void** bufs, long long T, long long B, int obs_dim, int act_dim, const long long* index, long long n, void** outs,
                               long long* bad) {
   const Buf b = make_buf(bufs, T, B, obs_dim, act_dim);
-  const long long blocks = (n + G_SAMPLES - 1) / G_SAMPLES;
-  std::vector<uint32_t> lds((size_t)G_SAMPLES * G_STRIDE);
+  const long long blocks = (n + TILE_ITEMS - 1) / TILE_ITEMS;
+  std::vector<uint32_t> lds(postpass::TILE_WORDS);
   for (long long blk = 0; blk < blocks; blk++) {
-    const long long s0 = blk * G_SAMPLES;
-    const int ns = tile_samples(n, blk);
-    Sample sm[G_SAMPLES];
+    const long long s0 = blk * TILE_ITEMS;
+    const int ns = postpass::tile_items(n, blk);
+    Sample sm[TILE_ITEMS] = {};
     for (int lane = 0; lane < ns; lane++) sm[lane] = split_index(index[s0 + lane], T, B);
     const float* ssrc[4] = {b.advantage, b.returns, b.value, b.log_prob};
     for (int wave = 0; wave < BLOCK / 64; wave++)
@@ -125,17 +111,11 @@ extern "C" int ro_host_gather(void** bufs, long long T, long long B, int obs_dim
       if (!out) continue;
       const uint32_t* src = is_obs ? (const uint32_t*)b.obs : b.action;
       const int dim = is_obs ? obs_dim : act_dim;
-      const int r0 = (is_obs ? g : g - obs_groups) * G_ROWS;
-      const int nr = dim - r0 < G_ROWS ? dim - r0 : G_ROWS;
-      for (int wave = 0; wave < BLOCK / 64; wave++)
-        for (int lane = 0; lane < ns; lane++)
-          for (int rr = wave; rr < nr; rr += BLOCK / 64) lds[lds_slot(lane, rr)] = sm[lane].ok ? src[soa_offset(sm[lane], dim, r0 + rr, B)] : 0u;
+      const int r0 = (is_obs ? g : g - obs_groups) * TILE_ROWS;
+      const int nr = postpass::group_rows(dim, r0);
       for (int t = 0; t < BLOCK; t++)
-        for (int e = t; e < ns * nr; e += BLOCK) {
-          int s, rr;
-          tile_elem(e, nr, &s, &rr);
-          out[(size_t)(s0 + s) * dim + r0 + rr] = lds[lds_slot(s, rr)];
-        }
+        if ((t & 63) < ns) thread_gather_stage(src, dim, r0, nr, sm[t & 63], B, t, lds.data());   // gather_rows, before the barrier
+      for (int t = 0; t < BLOCK; t++) postpass::tile_write(out, dim, r0, nr, (size_t)s0, ns, t, lds.data());      // ... and after it
     }
   }
   return 0;

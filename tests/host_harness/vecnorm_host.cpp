@@ -1,42 +1,26 @@
-// Host instantiation of the normalisation kernels' math (TEST HARNESS ONLY): the __host__ __device__ functions of csrc/vecnorm.hpp
-// compiled with g++, driven in the order the two launches run them -- every (row, chunk) block, every thread of it, the wave butterfly
-// and the four-wave sum of block_sum, the index-order merge of the partials -- so the CPU tests hold the kernels' arithmetic to the
-// oracle for any batch size without a GPU.
-#include <cstring>
+// Host instantiation of the normalisation kernels' math (TEST HARNESS ONLY): the __host__ __device__ functions of csrc/vecnorm.hpp (over
+// the block and chunk walk of csrc/postpass.hpp) compiled with g++, driven in the order the two launches run them -- every (row, chunk)
+// block, every thread of it, the wave butterfly and the four-wave sum of block_sum, the index-order merge of the partials -- so the CPU
+// tests hold the kernels' arithmetic to the oracle for any batch size without a GPU.
 #include <vector>
 
 #include "../../random-envs_amd/csrc/vecnorm.hpp"
+#include "block_sum_host.hpp"
 
 using namespace vecnorm;
 
-namespace {
+extern "C" int vn_host_chunks(long long B, int rows) { return postpass::chunk_count(B, rows); }
 
-// block_sum of vecnorm.hpp: __shfl_down butterfly (a lane past the wave's end reads itself), then the waves in index order
-template <int K>
-void block_sum_host(std::vector<double>& v /*[BLOCK][K]*/, double (&out)[K]) {
-  double wave_sum[BLOCK / 64][K];
-  for (int w = 0; w < BLOCK / 64; w++) {
-    double lane[64][K];
-    for (int l = 0; l < 64; l++)
-      for (int k = 0; k < K; k++) lane[l][k] = v[(size_t)(w * 64 + l) * K + k];
-    for (int off = 32; off; off >>= 1) {
-      double nxt[64][K];
-      for (int l = 0; l < 64; l++)
-        for (int k = 0; k < K; k++) nxt[l][k] = lane[l][k] + (l + off < 64 ? lane[l + off][k] : lane[l][k]);
-      memcpy(lane, nxt, sizeof lane);
-    }
-    for (int k = 0; k < K; k++) wave_sum[w][k] = lane[0][k];
-  }
-  for (int k = 0; k < K; k++) {
-    double s = wave_sum[0][k];
-    for (int w = 1; w < BLOCK / 64; w++) s += wave_sum[w][k];
-    out[k] = s;
-  }
+// counts[i / VEC] goes up for every group start i for_thread_groups hands out over all (chunk, t); returns the starts that are no multiple of VEC in [0, N)
+extern "C" long long vn_host_walk(long long N, int rows, int* counts /*[ceil(N / VEC)]*/) {
+  const int chunks = postpass::chunk_count(N, rows);
+  const long long tpc = postpass::tiles_per_chunk(N, chunks);
+  long long stray = 0;
+  for (int chunk = 0; chunk < chunks; chunk++)
+    for (int t = 0; t < BLOCK; t++)
+      postpass::for_thread_groups(N, chunk, tpc, t, [&](long long i) { (i < 0 || i >= N || i % VEC) ? stray++ : counts[i / VEC]++; });
+  return stray;
 }
-
-}  // namespace
-
-extern "C" int vn_host_chunks(long long B, int rows) { return chunk_count(B, rows); }
 
 // One rex_norm_step (mode 0) or rex_norm_reset (mode 1) on host arrays.  stats [3][obs_dim + 1] and the lane state are updated in place;
 // agg [4] accumulates (episodes, sum of returns, sum of lengths, non-finite elements).  cfg = {gamma, epsilon, clip_obs, clip_reward}.
@@ -45,8 +29,8 @@ extern "C" int vn_host_call(int mode, long long B, int obs_dim, const float* obs
                             double* ep_return, int32_t* ep_len, float* obs_out, float* reward_out, float* term_out, double* ep_return_out,
                             int32_t* ep_len_out, double* agg) {
   const int R = obs_dim + 1;
-  const int chunks = chunk_count(B, R);
-  const long long tpc = tiles_per_chunk(B, chunks);
+  const int chunks = postpass::chunk_count(B, R);
+  const long long tpc = postpass::tiles_per_chunk(B, chunks);
   const double gamma = cfg[0], eps = cfg[1], clip_obs = cfg[2], clip_reward = cfg[3];
   const bool have_obs = obs_in && obs_out;
   const bool norm_obs = norm_obs_flag && have_obs;

@@ -11,10 +11,10 @@ import pytest
 
 import eplog_oracle as oracle
 from eplog_oracle import assert_same_bits, assert_tables_equal
+from host_harness.build import build_so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(ROOT, "tests", "host_harness")
-HEADERS = [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in ("eplog.hpp", "vecnorm.hpp")]
 SIZES = [1, 63, 64, 257, 4097]
 GUARD = 16                      # elements behind every buffer of the table
 HOPPER_UNMODELED_MAP = [1, 2, 3]   # task row k = row 1 + k of the full hopper block (thigh, leg, foot masses; the torso mass is frozen)
@@ -26,11 +26,7 @@ def harness():
     """tests/host_harness/eplog_host.cpp built with g++ (rebuilt when it or a header is newer); no fused multiply-add"""
     global _lib
     if _lib is None:
-        src = os.path.join(HARNESS, "eplog_host.cpp")
-        so = os.path.join(HARNESS, "_build_eplog_host.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in [src] + HEADERS):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-        _lib = ctypes.CDLL(so)
+        _lib = ctypes.CDLL(build_so("eplog_host", "eplog_host.cpp", ["-ffp-contract=off"]))
         vp, ll, i32 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
         _lib.el_host_blocks.argtypes = [ll]
         _lib.el_host_step.argtypes = [vp, ll, ll, i32, vp, ll]

@@ -2,27 +2,18 @@
 incremental PGS) compiled for the host, against the independent 3-D oracle (world-frame Jacobian sums,
 dual PGS with an explicit A matrix)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness.build import build_so
 from oracle_bindings import _p, lib, oracle_energy_drift, oracle_humanoid_step
 from random_envs_amd.specs import SPECS
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "host_harness", "_build_humanoid_host.so")
-SRC = os.path.join(HERE, "host_harness", "humanoid_host.cpp")
-DEPS = [SRC] + [os.path.join(os.path.dirname(HERE), "random-envs_amd", "csrc", f) for f in
-                ("humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp", "probes.hpp")]
 
 
 @pytest.fixture(scope="module")
 def hh():
-    if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", SO, SRC])
-    return ctypes.CDLL(SO)
+    return ctypes.CDLL(build_so("humanoid_host", "humanoid_host.cpp"))
 
 
 def _states(n, seed, spread=0.3):
@@ -128,10 +119,7 @@ def test_second_broad_phase_test_never_changes_a_result(hh):
     """The projected segment-distance bounds of the broad phase (humanoid_engine.hpp::collide) only ever drop pairs the
     narrow phase would find apart: a harness built without them (-DREX_NO_SECOND_CULL) gives the same contacts, the same
     rows and bit-identical accelerations -- standing, crouched, lying and crumpled bodies, random orientations."""
-    so2 = SO.replace(".so", "_nocull.so")
-    if not os.path.exists(so2) or any(os.path.getmtime(d) > os.path.getmtime(so2) for d in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DREX_NO_SECOND_CULL", "-o", so2, SRC])
-    ref = ctypes.CDLL(so2)
+    ref = ctypes.CDLL(build_so("humanoid_host_nocull", "humanoid_host.cpp", ["-DREX_NO_SECOND_CULL"]))
     rng = np.random.RandomState(11)
     n = 3000
     q, v, a, xi = _states(n, 12, spread=0.3)
@@ -156,10 +144,7 @@ def test_fp32_host_engine_at_the_device_sweep_schedule(hh):
     built with -DREX_PGS_CHECK_HOST runs the fp32 engine at the DEVICE's schedule: sweep counts are then the every-sweep counts rounded up to
     the next multiple of 10 (never past MuJoCo's cap of 50), and one env step still agrees with the fp64 oracle within the fp32 tolerance the
     GPU tests use -- the extra sweeps act on a system already converged to the tolerance."""
-    so3 = os.path.join(HERE, "host_harness", "_build_humanoid_host_devsched.so")
-    if not os.path.exists(so3) or any(os.path.getmtime(d) > os.path.getmtime(so3) for d in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DREX_PGS_CHECK_HOST", "-o", so3, SRC])
-    hd = ctypes.CDLL(so3)
+    hd = ctypes.CDLL(build_so("humanoid_host_devsched", "humanoid_host.cpp", ["-DREX_PGS_CHECK_HOST"]))
     rng = np.random.RandomState(3)
     nom = np.array(SPECS["humanoid"].nominal_task)
     I = ctypes.POINTER(ctypes.c_int)

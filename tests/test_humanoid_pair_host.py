@@ -3,28 +3,20 @@
 fp64 oracle: a whole env step (20 forward evaluations, RK4), the 376-dim observation, reward, done; standing, crouched and
 piled-up states (all three solver paths); fp64 pins the algorithm, fp32 sets the GPU tolerance."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness.build import build_so
 from oracle_bindings import _p, oracle_humanoid_reset_obs, oracle_humanoid_step
 from random_envs_amd.specs import SPECS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "host_harness", "_build_humanoid_pair_host.so")
-SRC = os.path.join(HERE, "host_harness", "humanoid_pair_host.cpp")
-DEPS = [SRC] + [os.path.join(os.path.dirname(HERE), "random-envs_amd", "csrc", f) for f in
-                ("humanoid_pair.hpp", "humanoid_engine.hpp", "humanoid_model.hpp", "planar_spec.hpp", "probes.hpp")]
 UB = ctypes.POINTER(ctypes.c_ubyte); I = ctypes.POINTER(ctypes.c_int)
 
 
 @pytest.fixture(scope="module")
 def hp():
-    if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-pthread", "-o", SO, SRC])
-    return ctypes.CDLL(SO)
+    return ctypes.CDLL(build_so("humanoid_pair_host", "humanoid_pair_host.cpp", ["-pthread"]))
 
 
 def _step(hp, f32, q, v, a, xi, xprev=None):

@@ -3,14 +3,10 @@ sharding.shape_for_batch, the Python restatement that pinned shards rely on for 
 shows; the precedence of the tuning knobs, the shape request / report of the C-ABI and the reset plan of a step as literal tables."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
-HEADERS = [os.path.join(ROOT, "random-envs_amd", "csrc", "launch_shape.hpp"), os.path.join(ROOT, "include", "rex.h")]
+from host_harness.build import build_so
 
 KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
 KNOBS = ("REX_LANES", "REX_PAIR", "REX_ROLLED", "REX_HUM_PAIR", "REX_HUM_FUSED_RESET", "REX_FUSED_DERIVE", "REX_FAST")
@@ -26,11 +22,7 @@ def harness():
     """tests/host_harness/shape_host.cpp built with g++ (rebuilt when it or a header is newer)"""
     global _lib
     if _lib is None:
-        src = os.path.join(HARNESS, "shape_host.cpp")
-        so = os.path.join(HARNESS, "_build_shape_host.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in [src] + HEADERS):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", so, src])
-        _lib = ctypes.CDLL(so)
+        _lib = ctypes.CDLL(build_so("shape_host", "shape_host.cpp", ["-Wall", "-Werror"]))
         vp, ll, i32 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
         _lib.sh_why.restype = ctypes.c_char_p
         _lib.sh_choose.argtypes = [i32, ll, i32, vp, vp, vp]

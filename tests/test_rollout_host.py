@@ -3,17 +3,13 @@ csrc/rollout.hpp, driven in grid order by tests/host_harness/rollout_host.cpp) a
 tests/rollout_oracle.py.  GAE, the stored rows, the bootstrapped reward and the gather are held to IDENTICAL BITS; the moments to
 the bound of tests/test_vecnorm_host.py (n <= 2^22 fp64 terms err by n 2^-53 ~ 5e-10 < 1e-9), normalised advantages to 1 fp32 ulp."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rollout_oracle as oracle
+from host_harness.build import build_so
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
-HEADERS = [os.path.join(ROOT, "random-envs_amd", "csrc", f) for f in ("rollout.hpp", "vecnorm.hpp")]
 FIELDS = ("obs", "action", "reward", "value", "log_prob", "advantage", "returns", "done")
 
 _lib = None
@@ -23,13 +19,11 @@ def harness():
     """tests/host_harness/rollout_host.cpp built with g++ (rebuilt when it or a header is newer); no fused multiply-add"""
     global _lib
     if _lib is None:
-        src = os.path.join(HARNESS, "rollout_host.cpp")
-        so = os.path.join(HARNESS, "_build_rollout_host.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in [src] + HEADERS):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-        _lib = ctypes.CDLL(so)
+        _lib = ctypes.CDLL(build_so("rollout_host", "rollout_host.cpp", ["-ffp-contract=off"]))
         vp, ll, i32, f64 = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_double
         _lib.ro_host_parts.argtypes = [ll]
+        _lib.ro_host_tile.argtypes = [vp, i32, i32, vp, i32, i32]
+        _lib.ro_host_tile.restype = None
         _lib.ro_host_add.argtypes = [vp, ll, ll, i32, i32, ll, vp, f64, i32]
         _lib.ro_host_gae.argtypes = [vp, ll, ll, vp, f64, f64]
         _lib.ro_host_adv_stats.argtypes = [vp, ll, i32, i32, vp]
@@ -259,6 +253,20 @@ def test_moments_leave_out_and_count_non_finite_elements():
 
 
 # ------------------------------------------------------------------------------------------------- gather
+@pytest.mark.parametrize("nr", [1, 63, 64])
+@pytest.mark.parametrize("n", [1, 63, 64])
+def test_lds_tile_round_trip_is_the_transpose(n, nr):
+    """postpass.hpp's tile_stage / tile_write on one block: a source whose word encodes (item, row) comes out transposed in rows
+    [r0, r0 + nr) of the first n items of an exactly sized destination; every other word keeps its sentinel"""
+    dim, r0, sentinel = nr + 5, 3, 0xDEADBEEF
+    item, row = np.meshgrid(np.arange(n, dtype=np.uint32), np.arange(nr, dtype=np.uint32))      # [nr][n]
+    src = np.ascontiguousarray((item << 16) | row)
+    dst = np.full((n, dim), sentinel, dtype=np.uint32)
+    harness().ro_host_tile(src.ctypes.data, n, nr, dst.ctypes.data, dim, r0)
+    assert np.array_equal(dst[:, r0:r0 + nr], src.T)
+    assert np.all(dst[:, :r0] == sentinel) and np.all(dst[:, r0 + nr:] == sentinel)
+
+
 @pytest.mark.parametrize("T,B,D,A,discrete", [(7, 63, 11, 3, False), (3, 63, 376, 17, False), (5, 130, 4, 1, True), (1, 1, 1, 1, False), (2, 64, 65, 64, False)])
 def test_gather_equals_fancy_indexing(T, B, D, A, discrete):
     rng = np.random.default_rng(D)

@@ -3,15 +3,14 @@ kernels' own arithmetic (the __host__ __device__ functions of csrc/vecnorm.hpp, 
 tests/host_harness/vecnorm_host.cpp) to the oracle under the tolerances of tests/test_gpu_vecnorm.py."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_harness.build import build_so
 from vecnorm_oracle import VecNormOracle, f32_ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
 HEADER = os.path.join(ROOT, "random-envs_amd", "csrc", "vecnorm.hpp")
 
 
@@ -150,15 +149,13 @@ _lib = None
 
 
 def harness():
-    """tests/host_harness/vecnorm_host.cpp built with g++ (rebuilt when it or the header is newer)"""
+    """tests/host_harness/vecnorm_host.cpp built with g++ (rebuilt when it or a header is newer)"""
     global _lib
     if _lib is None:
-        src = os.path.join(HARNESS, "vecnorm_host.cpp")
-        so = os.path.join(HARNESS, "_build_vecnorm_host.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in (src, HEADER)):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-        _lib = ctypes.CDLL(so)
+        _lib = ctypes.CDLL(build_so("vecnorm_host", "vecnorm_host.cpp", ["-ffp-contract=off"]))
         _lib.vn_host_chunks.argtypes = [ctypes.c_longlong, ctypes.c_int]
+        _lib.vn_host_walk.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
+        _lib.vn_host_walk.restype = ctypes.c_longlong
         vp = ctypes.c_void_p
         _lib.vn_host_call.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int] + [vp] * 6 + [ctypes.c_int] * 4 + [vp] * 10
     return _lib
@@ -255,6 +252,16 @@ def test_kernel_math_many_chunks_and_grid_stride():
         _check_step(h, o, obs, rew, done, term, "step %d" % k)
 
 
+@pytest.mark.parametrize("rows", [1, 12, 377])
+@pytest.mark.parametrize("N", [1, 3, 4, 1023, 1024, 1025, 5 * 1024 + 2])
+def test_chunk_walk_hands_out_every_group_once(N, rows):
+    """postpass.hpp's for_thread_groups over all (chunk, t) of the launch's own chunking: the group starts are exactly
+    {0, 4, 8, .. < N}, each handed out once"""
+    counts = np.zeros((N + 3) // 4, dtype=np.int32)
+    assert harness().vn_host_walk(N, rows, counts.ctypes.data) == 0
+    assert np.array_equal(counts, np.ones_like(counts))
+
+
 def test_kernel_math_masked_reset_and_nan():
     D, B = 4, 4097
     rng = np.random.default_rng(6)
@@ -313,7 +320,7 @@ def test_package_exports_the_wrapper_and_the_abi_declares_the_calls():
     assert want <= set(_native.SYMBOLS)
     hdr = open(os.path.join(ROOT, "include", "rex.h")).read()
     assert all(w + "(" in hdr for w in want)
-    src = open(HEADER).read()
+    src = open(HEADER).read() + open(os.path.join(os.path.dirname(HEADER), "postpass.hpp")).read()   # the chunking and block_sum moved there
     assert "getenv" not in src
 
 
