@@ -4,6 +4,7 @@
 // results do not depend on how a batch is sharded over GPUs and no RNG state is stored.  The reset kernels and rex_sample_task draw through
 // rocRAND's engine (EngineRng); the planar step kernel's fused reset and observation noise evaluate the same word stream in registers
 // (philox_block, PhiloxWords).  The two paths share no code on purpose: tests/test_gpu_fused_reset_bits.py holds one against the other.
+// The absolute reference of both -- which word of which stream becomes which number -- is tests/rng_oracle.py, held by tests/test_gpu_rng_streams.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocrand/rocrand_kernel.h>
