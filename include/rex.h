@@ -430,6 +430,68 @@ int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index,
 /* out [host, 1 int64]: out-of-range ids rex_rbuf_gather met since the last clearing read.  Synchronises. */
 int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear);
 
+/* ---- prioritised replay: per-transition priorities, a sum tree, stratified proportional draws, priority updates --------------------
+ * Proportional prioritised experience replay (Schaul et al. 2016, "Prioritized Experience Replay") beside rex_rbuf_*, which stays as it
+ * is: the caller of rex_rbuf_gather that draws ids with probability priority / sum of priorities.  No reference counterpart of its own.
+ *
+ * Storage belongs to the caller, in device memory, for the N = T * B transition ids s = t * B + b of rex_rbuf_* (N <= 2^30, else
+ * REX_ERR_ARG):
+ *   priority     [N] f32.  A valid priority is finite and > 0; +0.0f marks a slot that is never drawn (empty, or given an invalid value).
+ *   tree         [rex_per_tree_len(N)] f64, a 64-ary sum tree.  n_0 = N, n_l = ceil(n_(l-1) / 64) up to the level D >= 1 with n_D = 1
+ *                (N = 1 still has a root above its leaf); the array holds the n_1 nodes of level 1 first and the root last;
+ *                rex_per_tree_len(N) = sum of n_l over l >= 1 (a host function without a handle; N outside [1, 2^30]: REX_ERR_ARG, i.e. D <= 5).
+ *                Node m of level l is the fp64 sum of its children 64 m .. 64 m + 63 of level l - 1 (leaves widened from f32), formed
+ *                SERIALLY in index order starting from 0.0; children past n_(l-1) count as 0.0.  That order is the whole definition of a
+ *                node's bits: an incremental update, rex_per_rebuild and a restatement in numpy agree bit for bit.
+ *   max_priority [1] f32: the largest valid priority seen since rex_per_init (at least 1.0f); what a new transition gets.
+ * The handle contributes the device and B and holds no buffer state.  rex_per_enable makes the only allocation (two device counters; it
+ * synchronises); every other rex_per_* call that takes a handle returns REX_ERR_STATE before it.  The launching calls neither allocate nor
+ * synchronise and keep no host state that changes between calls -- slot, seed and draw number are arguments, so a captured loop
+ * replays.  The number of launches of a call depends on D only and is given beside it.  No float atomics and no waiting between blocks:
+ * the launch boundary is the barrier; the only atomics are integer atomicMax on the bit patterns of non-negative finite floats (which
+ * order like unsigned integers) and integer atomicAdd on the counters.  Two threads that refresh the same node store identical bits. */
+typedef struct rex_per_buffers {
+  float* priority;
+  double* tree;
+  float* max_priority;
+  int64_t T;
+} rex_per_buffers;
+int64_t rex_per_tree_len(int64_t N);
+int rex_per_enable(rex_t* h);
+/* ONE launch: priority <- +0.0f, tree <- 0.0, *max_priority <- 1.0f. */
+int rex_per_init(rex_t* h, const rex_per_buffers* buf, void* stream);
+/* The companion of rex_rbuf_add for slot t, 2 + max(D - 2, 0) launches: the B leaves t * B .. t * B + B - 1 take *max_priority as it
+ * stands in stream order, then every ancestor of them is recomputed (one launch per level below the top two over the nodes above the
+ * range, one single-block launch for levels max(1, D - 1) .. D).  t outside [0, T): REX_ERR_ARG. */
+int rex_per_add(rex_t* h, const rex_per_buffers* buf, int64_t t, void* stream);
+/* 3 + max(D - 2, 0) launches; index [dev, int64 n], priority [dev, f32 n].  Pair j with an id outside [0, N) is never dereferenced, is
+ * counted (rex_per_read_counters, out[1]) and plays no further part.  Otherwise a value that is not finite and > 0 becomes +0.0f and is
+ * counted as invalid (out[0]) unless it is +-0.  Leaf index[j] <- that value; when an id occurs more than once in one call the LARGEST
+ * of its new values is stored (not a max with the old leaf: launch 1 clears the touched leaves, launch 2 is an integer atomicMax on the
+ * bits).  *max_priority <- max(*max_priority, every valid new value stored).  Then every ancestor of a touched leaf is recomputed, as in
+ * rex_per_add with the nodes above index[j] in place of the range.  n == 0 does nothing. */
+int rex_per_update(rex_t* h, const rex_per_buffers* buf, const int64_t* index, const float* priority, int64_t n, void* stream);
+/* 1 + D launches: every node recomputed from the leaves as they are (one launch per level), *max_priority <- max(1.0f, every valid
+ * leaf).  For buffers restored from a checkpoint, and the cross-check of the incremental path. */
+int rex_per_rebuild(rex_t* h, const rex_per_buffers* buf, void* stream);
+/* Stratified proportional sampling, ONE launch, no host-side randomness.  Sample j (0-based) of n evaluates the Philox4x32-10 block of
+ * rex_rbuf_sample -- key (lo32(seed), hi32(seed)), counter (lo32(j), hi32(j), lo32(draw), hi32(draw)) -- and takes the two words that
+ * call leaves unused: u = w2 | (w3 << 32), U = (double)(u >> 11) * 2^-53, x = ((double)j + U) * (total / (double)n) with total = the
+ * root; every operation a separate IEEE fp64 operation.  Descent from the root: at a node with children v_0 .. v_63 start with r = 0 and
+ * walk k = 0 .. 63: if x < r + v_k choose k, set x <- x - r and descend, else r <- r + v_k.  If no child is chosen (rounding at the upper
+ * edge) choose the largest k with v_k > 0 and leave x as it is.  If no child is positive (total == 0): index_out[j] = -1, prob_out[j] = 0.
+ * Otherwise index_out[j] = the leaf reached (its priority is > 0) and prob_out[j] = (float)((double)priority[id] / total).
+ * index_out [dev, int64 n] and prob_out [dev, f32 n] are required when n > 0.  The result depends on (seed, draw, n, j) and the tree only. */
+int rex_per_draw(rex_t* h, const rex_per_buffers* buf, int64_t n, uint64_t seed, uint64_t draw, int64_t* index_out, float* prob_out,
+                 void* stream);
+/* TWO launches: the draw above, then the launch of rex_rbuf_gather over index_out (outputs and normalise as there; needs rex_rbuf_enable
+ * too, and the same T in both descriptions).  An id of -1 meets that launch's guard: zeros, counted in rex_rbuf_read_bad_indices. */
+int rex_per_sample(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_buffers* per, int64_t n, uint64_t seed, uint64_t draw,
+                   int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
+                   int64_t* index_out, float* prob_out, void* stream);
+/* out [host, 2 int64]: invalid priorities and out-of-range ids rex_per_update met since the last clearing read.  Synchronises. */
+int rex_per_read_counters(rex_t* h, int64_t* out, int clear);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

@@ -12,7 +12,8 @@ from .vec_env import VecRandomEnv  # noqa: F401
 from .normalize import NormalizedVecRandomEnv, merge_stats  # noqa: F401
 from .rollout import RolloutBuffer  # noqa: F401
 from .replay_buffer import ReplayBuffer  # noqa: F401
+from .prioritized_replay import PrioritizedReplayBuffer  # noqa: F401
 from .episode_log import EpisodeLog, merge_logs  # noqa: F401
 from . import _native  # noqa: F401
 
-__all__ = ["make", "registered_ids", "spec", "VecRandomEnv", "NormalizedVecRandomEnv", "merge_stats", "RolloutBuffer", "ReplayBuffer", "EpisodeLog", "merge_logs"]
+__all__ = ["make", "registered_ids", "spec", "VecRandomEnv", "NormalizedVecRandomEnv", "merge_stats", "RolloutBuffer", "ReplayBuffer", "PrioritizedReplayBuffer", "EpisodeLog", "merge_logs"]

@@ -23,6 +23,8 @@ SYMBOLS = [
     "rex_rollout_read_bad_indices",
     "rex_eplog_enable", "rex_eplog_step", "rex_eplog_sync", "rex_eplog_read", "rex_eplog_get_lane_state", "rex_eplog_set_lane_state",
     "rex_rbuf_enable", "rex_rbuf_add", "rex_rbuf_sample", "rex_rbuf_gather", "rex_rbuf_read_bad_indices",
+    "rex_per_tree_len", "rex_per_enable", "rex_per_init", "rex_per_add", "rex_per_update", "rex_per_rebuild", "rex_per_draw", "rex_per_sample",
+    "rex_per_read_counters",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -52,6 +54,10 @@ class RexEplogBuffers(ctypes.Structure):
 
 class RexRbufBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "next_obs", "action", "reward", "done", "timeout")] + [("T", ctypes.c_int64)]
+
+
+class RexPerBuffers(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("priority", "tree", "max_priority")] + [("T", ctypes.c_int64)]
 
 
 class RexError(RuntimeError):
@@ -135,6 +141,17 @@ def lib():
     L.rex_rbuf_sample.argtypes = [vp, rp, i64, i64, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rex_rbuf_gather.argtypes = [vp, rp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
     L.rex_rbuf_read_bad_indices.argtypes = [vp, ctypes.POINTER(i64), i32]
+    pp = ctypes.POINTER(RexPerBuffers)
+    L.rex_per_tree_len.argtypes = [i64]
+    L.rex_per_tree_len.restype = i64
+    L.rex_per_enable.argtypes = [vp]
+    L.rex_per_init.argtypes = [vp, pp, vp]
+    L.rex_per_add.argtypes = [vp, pp, i64, vp]
+    L.rex_per_update.argtypes = [vp, pp, vp, vp, i64, vp]
+    L.rex_per_rebuild.argtypes = [vp, pp, vp]
+    L.rex_per_draw.argtypes = [vp, pp, i64, u64, u64, vp, vp, vp]
+    L.rex_per_sample.argtypes = [vp, rp, pp, i64, u64, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_per_read_counters.argtypes = [vp, ctypes.POINTER(i64), i32]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

@@ -36,6 +36,7 @@
 #include "vecnorm.hpp"
 #include "rollout.hpp"
 #include "replay_buffer.hpp"
+#include "priority_replay.hpp"
 #include "eplog.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
@@ -138,6 +139,9 @@ struct rex_env {
   eplog::Params eplog{};
   // rex_rbuf_* (replay_buffer.hpp): the bad-index counter rex_rbuf_enable allocates.  Nothing else of a replay buffer lives in the handle.
   void* rbuf_mem = nullptr;
+  // rex_per_* (priority_replay.hpp): the two counters rex_per_enable allocates (invalid priorities, out-of-range update ids).  Priorities and
+  // the sum tree belong to the caller.
+  void* per_mem = nullptr;
 };
 constexpr size_t EV_POOL = 8192;
 
@@ -456,6 +460,7 @@ extern "C" int rex_destroy(rex_t* h) {
   if (h->rollout_mem) hipFree(h->rollout_mem);
   if (h->eplog_mem) hipFree(h->eplog_mem);
   if (h->rbuf_mem) hipFree(h->rbuf_mem);
+  if (h->per_mem) hipFree(h->per_mem);
   for (auto e : h->ev0) hipEventDestroy(e);
   for (auto e : h->ev1) hipEventDestroy(e);
   delete h;
@@ -1331,4 +1336,148 @@ extern "C" int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear) {
   REX_NEEDS(h, rbuf_mem, "rex_rbuf_read_bad_indices", "rex_rbuf_enable");
   if (!out) return set_err(REX_ERR_ARG, "rex_rbuf_read_bad_indices: null argument");
   return read_counter((unsigned long long*)h->rbuf_mem, out, clear);
+}
+
+// ------------------------------------------------------------------------------------------
+// prioritised replay (priority_replay.hpp): per-transition priorities under a 64-ary fp64 sum tree in caller-owned memory, stratified
+// proportional draws, priority updates
+// ------------------------------------------------------------------------------------------
+extern "C" int64_t rex_per_tree_len(int64_t N) {
+  per::Tree t;
+  if (!per::tree_of((long long)N, &t)) return set_err(REX_ERR_ARG, "rex_per_tree_len: N = %lld outside [1, 2^30]", (long long)N);
+  return (int64_t)t.len;
+}
+
+extern "C" int rex_per_enable(rex_t* h) {
+  REX_ENTER(h, "rex_per_enable");
+  if (!h->per_mem) HIP_TRY(hipMalloc(&h->per_mem, sizeof(unsigned long long) * per::N_COUNTERS));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemset(h->per_mem, 0, sizeof(unsigned long long) * per::N_COUNTERS));
+  return REX_OK;
+}
+
+// the caller's struct with the handle's batch and the tree's shape; every buffer is required
+static int per_buf(const rex_env* h, const rex_per_buffers* b, const char* fn, per::Buf* out) {
+  if (!b) return set_err(REX_ERR_ARG, "%s: null buffer description", fn);
+  if (!b->priority || !b->tree || !b->max_priority) return set_err(REX_ERR_ARG, "%s: every pointer of rex_per_buffers is required", fn);
+  if (b->T <= 0) return set_err(REX_ERR_ARG, "%s: T must be > 0 (got %lld)", fn, (long long)b->T);
+  *out = per::Buf{b->priority, b->tree, b->max_priority, (long long)b->T, h->B, {}};
+  if (b->T > per::MAX_LEAVES / h->B || !per::tree_of((long long)b->T * h->B, &out->tr))
+    return set_err(REX_ERR_ARG, "%s: T * batch = %lld * %lld is more than 2^30 transitions", fn, (long long)b->T, h->B);
+  return REX_OK;
+}
+
+static unsigned per_blocks(long long n, int block = per::BLOCK) { return (unsigned)((n + block - 1) / block); }
+
+// one launch per level below the top two over `n` threads -- the ancestors of index[0 .. n), or of the leaves [s0, s1] when index is
+// null -- then the single block that takes the top
+static void launch_per_refresh(const per::Buf& b, const long long* index, long long n, long long s0, long long s1, hipStream_t st) {
+  for (int l = 1; l < per::top_first_level(b.tr); l++) {
+    per::RefreshParams r{b, index, index ? n : per::range_count(s0, s1, l), index ? 0 : per::range_first(s0, l), l, 0};
+    hipLaunchKernelGGL(per::per_refresh_kernel, dim3(per_blocks(r.n)), dim3(per::BLOCK), 0, st, r);
+  }
+  hipLaunchKernelGGL(per::per_top_kernel, dim3(1), dim3(per::BLOCK), 0, st, b);
+}
+
+extern "C" int rex_per_init(rex_t* h, const rex_per_buffers* buf, void* stream) {
+  REX_ENTER(h, "rex_per_init");
+  REX_NEEDS(h, per_mem, "rex_per_init", "rex_per_enable");
+  per::Buf b;
+  if (int rc = per_buf(h, buf, "rex_per_init", &b)) return rc;
+  hipLaunchKernelGGL(per::per_init_kernel, dim3(per_blocks(per::init_items(b))), dim3(per::BLOCK), 0, (hipStream_t)stream, b, (int)per::INIT_ALL);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_per_add(rex_t* h, const rex_per_buffers* buf, int64_t t, void* stream) {
+  REX_ENTER(h, "rex_per_add");
+  REX_NEEDS(h, per_mem, "rex_per_add", "rex_per_enable");
+  per::Buf b;
+  if (int rc = per_buf(h, buf, "rex_per_add", &b)) return rc;
+  if (t < 0 || t >= buf->T) return set_err(REX_ERR_ARG, "rex_per_add: slot %lld outside [0, %lld)", (long long)t, (long long)buf->T);
+  hipLaunchKernelGGL(per::per_fill_kernel, dim3(per_blocks(b.B)), dim3(per::BLOCK), 0, (hipStream_t)stream, b, (long long)t);
+  launch_per_refresh(b, nullptr, 0, (long long)t * b.B, (long long)(t + 1) * b.B - 1, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_per_update(rex_t* h, const rex_per_buffers* buf, const int64_t* index, const float* priority, int64_t n, void* stream) {
+  REX_ENTER(h, "rex_per_update");
+  REX_NEEDS(h, per_mem, "rex_per_update", "rex_per_enable");
+  per::UpdateParams p{};
+  if (int rc = per_buf(h, buf, "rex_per_update", &p.buf)) return rc;
+  if (n < 0 || (n > 0 && (!index || !priority))) return set_err(REX_ERR_ARG, "rex_per_update: n must be >= 0 and index and priority given");
+  if (n == 0) return REX_OK;
+  if (!grid_fits((n + per::BLOCK - 1) / per::BLOCK)) return set_err(REX_ERR_ARG, "rex_per_update: n = %lld is more than one launch takes", (long long)n);
+  p.index = (const long long*)index; p.value = priority; p.n = n; p.counters = (unsigned long long*)h->per_mem;
+  const dim3 grid(per_blocks(n)), block(per::BLOCK);
+  hipLaunchKernelGGL(per::per_clear_kernel, grid, block, 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(per::per_scatter_kernel, grid, block, 0, (hipStream_t)stream, p);
+  launch_per_refresh(p.buf, p.index, n, 0, 0, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_per_rebuild(rex_t* h, const rex_per_buffers* buf, void* stream) {
+  REX_ENTER(h, "rex_per_rebuild");
+  REX_NEEDS(h, per_mem, "rex_per_rebuild", "rex_per_enable");
+  per::Buf b;
+  if (int rc = per_buf(h, buf, "rex_per_rebuild", &b)) return rc;
+  hipLaunchKernelGGL(per::per_init_kernel, dim3(1), dim3(per::BLOCK), 0, (hipStream_t)stream, b, (int)per::INIT_MAX);
+  for (int l = 1; l <= b.tr.D; l++) {
+    per::RefreshParams r{b, nullptr, b.tr.n[l], 0, l, l == 1 ? 1 : 0};
+    hipLaunchKernelGGL(per::per_refresh_kernel, dim3(per_blocks(r.n)), dim3(per::BLOCK), 0, (hipStream_t)stream, r);
+  }
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+// the draw launch of rex_per_draw and rex_per_sample
+static int launch_per_draw(const char* fn, const per::Buf& b, int64_t n, uint64_t seed, uint64_t draw, int64_t* index_out, float* prob_out, hipStream_t st) {
+  if (n < 0 || (n > 0 && (!index_out || !prob_out))) return set_err(REX_ERR_ARG, "%s: n must be >= 0 and index_out and prob_out given", fn);
+  if (n == 0) return REX_OK;
+  if (!grid_fits((n + per::DRAW_BLOCK - 1) / per::DRAW_BLOCK)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, (long long)n);
+  per::DrawParams p{b, (long long)n, seed, draw, (long long*)index_out, prob_out};
+  hipLaunchKernelGGL(per::per_draw_kernel, dim3(per_blocks(n, per::DRAW_BLOCK)), dim3(per::DRAW_BLOCK), 0, st, p);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_per_draw(rex_t* h, const rex_per_buffers* buf, int64_t n, uint64_t seed, uint64_t draw, int64_t* index_out, float* prob_out,
+                            void* stream) {
+  REX_ENTER(h, "rex_per_draw");
+  REX_NEEDS(h, per_mem, "rex_per_draw", "rex_per_enable");
+  per::Buf b;
+  if (int rc = per_buf(h, buf, "rex_per_draw", &b)) return rc;
+  return launch_per_draw("rex_per_draw", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream);
+}
+
+extern "C" int rex_per_sample(rex_t* h, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, int64_t n, uint64_t seed, uint64_t draw,
+                              int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
+                              int64_t* index_out, float* prob_out, void* stream) {
+  REX_ENTER(h, "rex_per_sample");
+  REX_NEEDS(h, per_mem, "rex_per_sample", "rex_per_enable");
+  REX_NEEDS(h, rbuf_mem, "rex_per_sample", "rex_rbuf_enable");
+  per::Buf b;
+  rbuf::SampleParams p{};
+  if (int rc = per_buf(h, buf, "rex_per_sample", &b)) return rc;
+  if (int rc = rbuf_buf(h, rb, "rex_per_sample", &p.buf)) return rc;
+  if (rb->T != buf->T) return set_err(REX_ERR_ARG, "rex_per_sample: the two descriptions disagree on T (%lld and %lld)", (long long)rb->T, (long long)buf->T);
+  if (normalise && !h->norm_mem) return set_err(REX_ERR_STATE, "rex_per_sample: normalise needs rex_norm_enable on this handle");
+  if (int rc = launch_per_draw("rex_per_sample", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream)) return rc;
+  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr};
+  p.index = (const long long*)index_out; p.n = n; p.N = p.buf.T * p.buf.B;
+  return launch_rbuf_sample(h, "rex_per_sample", p, normalise, (hipStream_t)stream);
+}
+
+extern "C" int rex_per_read_counters(rex_t* h, int64_t* out, int clear) {
+  REX_ENTER(h, "rex_per_read_counters");
+  REX_NEEDS(h, per_mem, "rex_per_read_counters", "rex_per_enable");
+  if (!out) return set_err(REX_ERR_ARG, "rex_per_read_counters: null argument");
+  unsigned long long v[per::N_COUNTERS] = {0, 0};
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(v, h->per_mem, sizeof v, hipMemcpyDeviceToHost));
+  out[0] = (int64_t)v[per::C_INVALID]; out[1] = (int64_t)v[per::C_BAD_ID];
+  if (clear) HIP_TRY(hipMemset(h->per_mem, 0, sizeof v));
+  return REX_OK;
 }

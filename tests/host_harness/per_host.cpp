@@ -1,0 +1,126 @@
+// Host instantiation of the prioritised replay kernels' math (TEST HARNESS ONLY): the __host__ __device__ functions of
+// csrc/priority_replay.hpp compiled with g++ -ffp-contract=off and driven in the order the launches of rex_per_* run them -- launch by
+// launch, every block of the grid, every thread of it; the integer atomicMax / atomicAdd of the scatter launch restated as max / += -- so
+// the CPU tests hold the kernels' arithmetic and addressing to the oracle for any size without a GPU.
+#include <cstdint>
+
+#include "../../random-envs_amd/csrc/priority_replay.hpp"
+
+using namespace per;
+
+namespace {
+
+// p: priority, tree, max_priority
+bool make_buf(void** p, long long T, long long B, Buf* b) {
+  *b = Buf{(float*)p[0], (double*)p[1], (float*)p[2], T, B, {}};
+  return T > 0 && B > 0 && T <= MAX_LEAVES / B && tree_of(T * B, &b->tr);
+}
+
+long long blocks_of(long long n, int block = BLOCK) { return (n + block - 1) / block; }
+
+// a launch of `n` threads in blocks of `block`
+template <class F>
+void launch(long long n, int block, F&& thread) {
+  for (long long blk = 0; blk < blocks_of(n, block); blk++)
+    for (int t = 0; t < block; t++) {
+      const long long i = blk * block + t;
+      if (i < n) thread(i);
+    }
+}
+
+// launch_per_refresh of rex_hip.hip: one launch per level below the top two, then the single block
+void refresh(const Buf& b, const long long* index, long long n, long long s0, long long s1) {
+  for (int l = 1; l < top_first_level(b.tr); l++) {
+    const long long first = index ? 0 : range_first(s0, l), count = index ? n : range_count(s0, s1, l);
+    launch(count, BLOCK, [&](long long j) {
+      const long long m = refresh_target(b, index, first, l, j);
+      if (m >= 0) refresh_node(b, l, m);
+    });
+  }
+  for (int l = top_first_level(b.tr); l <= b.tr.D; l++)
+    for (int t = 0; t < BLOCK; t++) thread_top(b, l, t);
+}
+
+}  // namespace
+
+extern "C" long long per_host_tree_len(long long N) {
+  Tree t;
+  return tree_of(N, &t) ? t.len : -1;
+}
+extern "C" int per_host_depth(long long N) {
+  Tree t;
+  return tree_of(N, &t) ? t.D : -1;
+}
+
+extern "C" int per_host_init(void** p, long long T, long long B) {
+  Buf b;
+  if (!make_buf(p, T, B, &b)) return -1;
+  launch(init_items(b), BLOCK, [&](long long i) { thread_init(b, INIT_ALL, i); });
+  return 0;
+}
+
+extern "C" int per_host_add(void** p, long long T, long long B, long long t) {
+  Buf b;
+  if (!make_buf(p, T, B, &b) || t < 0 || t >= T) return -1;
+  launch(B, BLOCK, [&](long long i) { thread_fill(b, t, i); });
+  refresh(b, nullptr, 0, t * B, (t + 1) * B - 1);
+  return 0;
+}
+
+// counters: invalid priorities, out-of-range ids
+extern "C" int per_host_update(void** p, long long T, long long B, const long long* index, const float* value, long long n, long long* counters) {
+  Buf b;
+  if (!make_buf(p, T, B, &b) || n < 0) return -1;
+  if (n == 0) return 0;
+  launch(n, BLOCK, [&](long long j) { thread_clear(b, index, j); });
+  launch(n, BLOCK, [&](long long j) {
+    const Scatter s = scatter_of(b, index, value, j);
+    if (s.count >= 0) counters[s.count] += 1;
+    if (s.leaf >= 0) {
+      uint32_t* leaf = reinterpret_cast<uint32_t*>(b.priority + s.leaf);
+      uint32_t* top = reinterpret_cast<uint32_t*>(b.max_priority);
+      if (s.bits > *leaf) *leaf = s.bits;
+      if (s.bits > *top) *top = s.bits;
+    }
+  });
+  refresh(b, index, n, 0, 0);
+  return 0;
+}
+
+extern "C" int per_host_rebuild(void** p, long long T, long long B) {
+  Buf b;
+  if (!make_buf(p, T, B, &b)) return -1;
+  launch(1, BLOCK, [&](long long i) { thread_init(b, INIT_MAX, i); });
+  for (int l = 1; l <= b.tr.D; l++)
+    launch(b.tr.n[l], BLOCK, [&](long long j) {
+      const long long m = refresh_target(b, nullptr, 0, l, j);
+      refresh_node(b, l, m);
+      if (l == 1) {
+        const uint32_t mx = leaf_max_bits(b, m);
+        uint32_t* top = reinterpret_cast<uint32_t*>(b.max_priority);
+        if (mx > ONE_BITS && mx > *top) *top = mx;
+      }
+    });
+  return 0;
+}
+
+extern "C" int per_host_draw(void** p, long long T, long long B, long long n, unsigned long long seed, unsigned long long draw, long long* index_out,
+                             float* prob_out) {
+  Buf b;
+  if (!make_buf(p, T, B, &b) || n < 0) return -1;
+  launch(n, DRAW_BLOCK, [&](long long j) { lane_draw(b, n, seed, draw, j, index_out, prob_out); });
+  return 0;
+}
+
+extern "C" double per_host_x(unsigned long long seed, unsigned long long draw, unsigned long long j, long long n, double total) {
+  return sample_x(seed, draw, j, n, total);
+}
+
+// the descent alone from the caller's x [n]
+extern "C" int per_host_descent(void** p, long long T, long long B, const double* x, long long n, long long* index_out, float* prob_out) {
+  Buf b;
+  if (!make_buf(p, T, B, &b)) return -1;
+  const double total = b.tree[b.tr.len - 1];
+  for (long long j = 0; j < n; j++) descent(b, x[j], total, index_out + j, prob_out + j);
+  return 0;
+}
