@@ -492,6 +492,56 @@ int rex_per_sample(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_buffers
 /* out [host, 2 int64]: invalid priorities and out-of-range ids rex_per_update met since the last clearing read.  Synchronises. */
 int rex_per_read_counters(rex_t* h, int64_t* out, int clear);
 
+/* ---- n-step returns sampled from the replay buffer ---------------------------------------------------------------------------------
+ * The n-step variant of rex_rbuf_sample / rex_rbuf_gather / rex_per_sample, which stay as they are: what Rainbow, D4PG, R2D2 and n-step
+ * SAC / TD3 bootstrap from, r_0 + gamma r_1 + ... + gamma^(m-1) r_(m-1) + gamma^m Q(s_m), formed inside the launch that copies the rows.
+ * Storage, handle, rex_rbuf_enable and the rules of the family are those of rex_rbuf_*: REX_ERR_STATE before rex_rbuf_enable, no
+ * allocation, no synchronisation, no host state between calls, n == 0 does nothing.
+ *
+ * New arguments: n_step, an int in [1, 32]; gamma, a finite double in [0, 1]; head, an int64 in [0, T): the slot written most recently.
+ * Anything else is REX_ERR_ARG.
+ *
+ * Sample j has the guarded id s, with t0 = s / B and b = s % B.  Its window is the steps k = 0, 1, ... with t_k = (t0 + k) mod T and
+ * s_k = t_k * B + b (the next step of the same env lies B ids further on, modulo T * B).  Step k is the LAST step of the window (so
+ * m = k + 1) when the first of these holds:
+ *   done[s_k] != 0 || timeout[s_k] != 0   the episode ends there;
+ *   t_k == head                           the next slot holds the oldest data of a full ring, or nothing at all;
+ *   k == n_step - 1.
+ * Every operand is widened to fp64 and every operation is a separate IEEE fp64 operation, never contracted:
+ *   acc = reward[s_0];  g = gamma;
+ *   for k = 1 .. m-1:   acc = acc + g * reward[s_k];   g = g * gamma;
+ * Outputs, each optional (NULL skips), in the layout of rex_rbuf_gather:
+ *   obs_out[j]      = the obs row of s_0;            action_out[j] = the action row of s_0;
+ *   next_obs_out[j] = the next_obs row of s_(m-1);
+ *   reward_out[j]   = (float)acc;
+ *   done_out[j]     = (done[s_(m-1)] && !timeout[s_(m-1)]) ? 1 : 0 (a window cut by the head or by a time limit still bootstraps);
+ *   discount_out[j] = (float)g, that is gamma^m: what the learner multiplies its target value by;   [n] f32
+ *   steps_out[j]    = m;                                                                              [n] int32
+ *   index_out[j]    = s in the sampling calls.
+ * normalise != 0 behaves as in rex_rbuf_sample: obs / next_obs are normalised with the running statistics as they stand; reward_out is
+ * the normalisation of the float32 n-step sum with the return row's statistic -- the return is normalised once, not each term;
+ * discount_out, steps_out and done_out are never normalised.
+ * An id outside [0, T * B) is never turned into an address: every output of that sample is zero, discount_out and steps_out included,
+ * and it is counted in the counter rex_rbuf_read_bad_indices reads.
+ * With n_step == 1 the five outputs the plain launch has are bit-identical to rex_rbuf_gather for any head, discount_out is
+ * (float)gamma and steps_out is 1. */
+/* ONE launch over the caller's ids: index [dev, int64 n]. */
+int rex_rbuf_gather_nstep(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int64_t head, int n_step, double gamma,
+                          int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
+                          float* discount_out, int32_t* steps_out, void* stream);
+/* ONE launch.  The ids are exactly those of rex_rbuf_sample for the same (seed, draw, size, B, j); every stored id is a valid start,
+ * because the window shortens instead.  size outside [1, T], or size < T && head != size - 1 (a ring that has not wrapped was filled from
+ * slot 0): REX_ERR_ARG. */
+int rex_rbuf_sample_nstep(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t head, int64_t n, uint64_t seed, uint64_t draw,
+                          int n_step, double gamma, int normalise, float* obs_out, float* next_obs_out, void* action_out,
+                          float* reward_out, float* done_out, float* discount_out, int32_t* steps_out, int64_t* index_out, void* stream);
+/* TWO launches: the unchanged launch of rex_per_draw, then the n-step launch over index_out (needs rex_per_enable too, and the same T
+ * in both descriptions).  An id of -1 meets the guard: zeros, counted. */
+int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_buffers* per, int64_t n, int64_t head, uint64_t seed,
+                         uint64_t draw, int n_step, double gamma, int normalise, float* obs_out, float* next_obs_out, void* action_out,
+                         float* reward_out, float* done_out, float* discount_out, int32_t* steps_out, int64_t* index_out, float* prob_out,
+                         void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

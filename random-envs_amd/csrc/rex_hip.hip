@@ -37,6 +37,7 @@
 #include "rollout.hpp"
 #include "replay_buffer.hpp"
 #include "priority_replay.hpp"
+#include "nstep_replay.hpp"
 #include "eplog.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
@@ -1480,4 +1481,89 @@ extern "C" int rex_per_read_counters(rex_t* h, int64_t* out, int clear) {
   out[0] = (int64_t)v[per::C_INVALID]; out[1] = (int64_t)v[per::C_BAD_ID];
   if (clear) HIP_TRY(hipMemset(h->per_mem, 0, sizeof v));
   return REX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// n-step returns from the replay buffer (nstep_replay.hpp): the sample / gather launch with a window of up to 32 steps behind every id
+// ------------------------------------------------------------------------------------------
+// the window arguments every n-step call takes
+static int nstep_win(const char* fn, const rbuf::Buf& b, int64_t head, int n_step, double gamma, nstep::Win* out) {
+  if (n_step < 1 || n_step > nstep::MAX_STEPS) return set_err(REX_ERR_ARG, "%s: n_step %d outside [1, %d]", fn, n_step, nstep::MAX_STEPS);
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return set_err(REX_ERR_ARG, "%s: gamma %g is not a finite number in [0, 1]", fn, gamma);
+  if (head < 0 || head >= b.T) return set_err(REX_ERR_ARG, "%s: head %lld outside [0, %lld)", fn, (long long)head, b.T);
+  *out = nstep::Win{(long long)head, n_step, gamma};
+  return REX_OK;
+}
+
+// the one launch behind rex_rbuf_sample_nstep (index == nullptr: the ids are drawn), rex_rbuf_gather_nstep and rex_per_sample_nstep
+static int launch_rbuf_nstep(const rex_env* h, const char* fn, nstep::Params p, int normalise, hipStream_t st) {
+  if (normalise) {
+    if (!h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
+    const rex_norm_config& c = h->norm_cfg;
+    p.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
+  }
+  if (p.n == 0) return REX_OK;
+  const long long blocks = rbuf::sample_blocks(p.n);
+  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
+  const rbuf::Buf& b = p.buf;
+  const rbuf::Out& o = p.out.base;
+  p.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, o.obs, o.next_obs)) ? 1 : 0;
+  p.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, o.action)) ? 1 : 0;
+  p.bad = (unsigned long long*)h->rbuf_mem;
+  hipLaunchKernelGGL(nstep::rb_nstep_kernel, dim3((unsigned)blocks), dim3(nstep::BLOCK), 0, st, p);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+extern "C" int rex_rbuf_gather_nstep(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int64_t head, int n_step, double gamma,
+                                     int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
+                                     float* discount_out, int32_t* steps_out, void* stream) {
+  REX_ENTER(h, "rex_rbuf_gather_nstep");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_gather_nstep", "rex_rbuf_enable");
+  nstep::Params p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather_nstep", &p.buf)) return rc;
+  if (int rc = nstep_win("rex_rbuf_gather_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
+  if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rbuf_gather_nstep: n must be >= 0 and index given");
+  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr}, discount_out, steps_out};
+  p.index = (const long long*)index; p.n = n; p.N = p.buf.T * p.buf.B;
+  return launch_rbuf_nstep(h, "rex_rbuf_gather_nstep", p, normalise, (hipStream_t)stream);
+}
+
+extern "C" int rex_rbuf_sample_nstep(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t head, int64_t n, uint64_t seed, uint64_t draw,
+                                     int n_step, double gamma, int normalise, float* obs_out, float* next_obs_out, void* action_out,
+                                     float* reward_out, float* done_out, float* discount_out, int32_t* steps_out, int64_t* index_out, void* stream) {
+  REX_ENTER(h, "rex_rbuf_sample_nstep");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_sample_nstep", "rex_rbuf_enable");
+  nstep::Params p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample_nstep", &p.buf)) return rc;
+  if (int rc = nstep_win("rex_rbuf_sample_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
+  if (size < 1 || size > buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: size %lld outside [1, %lld]", (long long)size, (long long)buf->T);
+  if (size < buf->T && head != size - 1)
+    return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: a ring that is not full (size %lld < %lld) has head == size - 1, not %lld", (long long)size,
+                   (long long)buf->T, (long long)head);
+  if (n < 0) return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: n must be >= 0");
+  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, (long long*)index_out}, discount_out,
+                     steps_out};
+  p.n = n; p.N = (long long)size * h->B; p.seed = seed; p.draw = draw;
+  return launch_rbuf_nstep(h, "rex_rbuf_sample_nstep", p, normalise, (hipStream_t)stream);
+}
+
+extern "C" int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, int64_t n, int64_t head, uint64_t seed, uint64_t draw,
+                                    int n_step, double gamma, int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out,
+                                    float* done_out, float* discount_out, int32_t* steps_out, int64_t* index_out, float* prob_out, void* stream) {
+  REX_ENTER(h, "rex_per_sample_nstep");
+  REX_NEEDS(h, per_mem, "rex_per_sample_nstep", "rex_per_enable");
+  REX_NEEDS(h, rbuf_mem, "rex_per_sample_nstep", "rex_rbuf_enable");
+  per::Buf b;
+  nstep::Params p{};
+  if (int rc = per_buf(h, buf, "rex_per_sample_nstep", &b)) return rc;
+  if (int rc = rbuf_buf(h, rb, "rex_per_sample_nstep", &p.buf)) return rc;
+  if (rb->T != buf->T)
+    return set_err(REX_ERR_ARG, "rex_per_sample_nstep: the two descriptions disagree on T (%lld and %lld)", (long long)rb->T, (long long)buf->T);
+  if (int rc = nstep_win("rex_per_sample_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
+  if (normalise && !h->norm_mem) return set_err(REX_ERR_STATE, "rex_per_sample_nstep: normalise needs rex_norm_enable on this handle");
+  if (int rc = launch_per_draw("rex_per_sample_nstep", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream)) return rc;
+  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr}, discount_out, steps_out};
+  p.index = (const long long*)index_out; p.n = n; p.N = p.buf.T * p.buf.B;
+  return launch_rbuf_nstep(h, "rex_per_sample_nstep", p, normalise, (hipStream_t)stream);
 }

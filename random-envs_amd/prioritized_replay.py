@@ -57,11 +57,33 @@ class PrioritizedReplayBuffer(ReplayBuffer):
                                              self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]),
                                              self._p(out["reward"]), self._p(out["done"]), self._p(out["index"]), self._p(out["prob"]), self._stream()))
         self.draws += 1
+        return self._with_weight(out, beta)
+
+    def _with_weight(self, out, beta):
+        t = self._torch
         b = self.beta if beta is None else float(beta)
         w = (out["prob"] * float(len(self))).pow(-b)
         w = t.where(out["prob"] > 0, w, t.zeros_like(w))          # an id of -1 (nothing to draw) weighs nothing
-        out["weight"] = w / w.max().clamp_min(t.finfo(t.float32).tiny) if n else w
+        out["weight"] = w / w.max().clamp_min(t.finfo(t.float32).tiny) if out["prob"].numel() else w
         return out
+
+    def sample_nstep(self, batch_size, n_step, gamma, beta=None, normalize=None):
+        """:meth:`sample` with the n-step return of :meth:`ReplayBuffer.sample_nstep` behind every id, in two launches: the same draw
+        (``index`` and ``prob`` are those :meth:`sample` returns at the same draw number), then the n-step launch over its ids.  The dict
+        of :meth:`sample` plus ``discount`` and ``steps``."""
+        if len(self) == 0:
+            raise RuntimeError("PrioritizedReplayBuffer.sample_nstep: the buffer is empty")
+        t = self._torch
+        n = int(batch_size)
+        out = self._nstep_outputs(n, True)
+        out["prob"] = t.empty(n, dtype=t.float32, device=self.device)
+        _native.check(self._L.rex_per_sample_nstep(self._h, ctypes.byref(self._desc), ctypes.byref(self._per), n, self._head(), self.seed, self.draws,
+                                                   int(n_step), float(gamma), self._normalise_flag(normalize), self._p(out["obs"]),
+                                                   self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]),
+                                                   self._p(out["discount"]), self._p(out["steps"]), self._p(out["index"]), self._p(out["prob"]),
+                                                   self._stream()))
+        self.draws += 1
+        return self._with_weight(out, beta)
 
     def update_priorities(self, index, td_error):
         """Priority of transition ``index[j]`` <- ``(|td_error[j]| + eps) ** alpha`` (float32, computed by torch: a device ``powf`` would

@@ -7,7 +7,8 @@ of ``n_slots`` time slots over the env's batch, TRANSITION-MAJOR (``obs`` / ``ne
 ``step_soa_full`` returns (terminal observations go into ``next_obs`` on the finished lanes), one launch draws the ids of a
 minibatch on the device (Philox4x32-10, no host randomness, no synchronisation) and copies the whole rows into the row-major
 ``[n, dim]`` layout a network reads, normalised with the running statistics of a ``NormalizedVecRandomEnv`` on request
-(``rex_rbuf_*`` of include/rex.h, csrc/replay_buffer.hpp).
+(``rex_rbuf_*`` of include/rex.h, csrc/replay_buffer.hpp).  ``sample_nstep`` / ``gather_nstep`` form an n-step return behind every id
+in the same single launch (csrc/nstep_replay.hpp).
 """
 import ctypes
 
@@ -108,6 +109,50 @@ class ReplayBuffer(Layer):
         _native.check(self._L.rex_rbuf_gather(self._h, ctypes.byref(self._desc), self._p(index), n, self._normalise_flag(normalize),
                                               self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]),
                                               self._p(out["done"]), self._stream()))
+        out["index"] = index
+        return out
+
+    # ------------------------------------------------------------------ learn, n-step
+    def _head(self):
+        """The slot written most recently: where every n-step window stops at the latest."""
+        return (self.pos - 1) % self.n_slots
+
+    def _nstep_outputs(self, n, with_index):
+        t = self._torch
+        out = self._outputs(n, with_index)
+        out["discount"] = t.empty(n, dtype=t.float32, device=self.device)
+        out["steps"] = t.empty(n, dtype=t.int32, device=self.device)
+        return out
+
+    def sample_nstep(self, batch_size, n_step, gamma, normalize=None):
+        """:meth:`sample` with an n-step return behind every id, still in ONE launch: the window of transition ``s`` follows its env
+        through the ring for at most ``n_step`` (1 .. 32) steps and ends early at a done, a time limit or the newest slot.  ``obs`` and
+        ``action`` are those of the first step, ``next_obs`` and ``done`` those of the last, ``reward`` is ``r_0 + gamma r_1 + ... +
+        gamma^(m-1) r_(m-1)`` (fp64 sum, one rounding), ``discount`` [n] float32 is ``gamma^m`` -- what the target value is multiplied
+        by -- and ``steps`` [n] int32 is ``m``.  The ids are those :meth:`sample` draws at the same draw number, and the two methods
+        share that number.  With ``normalize`` the return is normalised once, as a reward is."""
+        size = self.n_slots if self.full else self.pos
+        if size == 0:
+            raise RuntimeError("ReplayBuffer.sample_nstep: the buffer is empty")
+        n = int(batch_size)
+        out = self._nstep_outputs(n, True)
+        _native.check(self._L.rex_rbuf_sample_nstep(self._h, ctypes.byref(self._desc), size, self._head(), n, self.seed, self.draws, int(n_step),
+                                                    float(gamma), self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]),
+                                                    self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]), self._p(out["discount"]),
+                                                    self._p(out["steps"]), self._p(out["index"]), self._stream()))
+        self.draws += 1
+        return out
+
+    def gather_nstep(self, index, n_step, gamma, normalize=None):
+        """The same launch for the caller's ids, as :meth:`gather` is to :meth:`sample`.  An id out of range gives zeros (``discount``
+        and ``steps`` included) and is counted (:meth:`bad_indices`)."""
+        self._check_index(index)
+        n = index.numel()
+        out = self._nstep_outputs(n, False)
+        _native.check(self._L.rex_rbuf_gather_nstep(self._h, ctypes.byref(self._desc), self._p(index), n, self._head(), int(n_step), float(gamma),
+                                                    self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]),
+                                                    self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]), self._p(out["discount"]),
+                                                    self._p(out["steps"]), self._stream()))
         out["index"] = index
         return out
 

@@ -1,0 +1,263 @@
+"""N-step returns from the replay buffer, CPU half: the kernel's own arithmetic and addressing (the __host__ __device__ functions of
+csrc/nstep_replay.hpp, driven in grid order by tests/host_harness/nstep_host.cpp -- a half-wave per sample, the ballot and the shuffles
+as arrays) against the numpy float64 oracle of tests/nstep_replay_oracle.py.  Every field is held to IDENTICAL BITS (copies, exact
+integer arithmetic and one fp64 operation at a time on both sides) except normalised values, which are held within 1 fp32 ulp by
+assert_f32_within_one_ulp, the criterion of tests/test_replay_buffer_host.py."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import nstep_replay_oracle as oracle
+import replay_buffer_oracle as rb_oracle
+from host_harness import nstep as host
+from host_harness import rbuf as rb_host
+from test_replay_buffer_host import DIMS, SHAPES, filled, random_norm
+from test_rollout_host import assert_same_bits
+from test_vecnorm_host import assert_f32_within_one_ulp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HARNESS = os.path.join(ROOT, "tests", "host_harness")
+N_STEPS = (1, 3, 5)
+PLAIN = ("obs", "next_obs", "action", "reward", "done")
+# the two cases that must show every ending: (T, B, probability of a done, n_steps, heads, seed of the data)
+ENDINGS = dict(T=9, B=63, p_done=0.15, n_steps=(3, 5), heads=(0, 4, 8), seed=0)
+LONGEST = dict(T=40, B=5, p_done=0.02, n_steps=(32,), heads=(0, 20, 39), seed=0)
+N_IDS = 256
+
+
+def heads_of(T):
+    return sorted({0, T // 2, T - 1})
+
+
+def window_buffers(rng, T, B, D, A, p_done, act_dtype=np.float32):
+    """test_replay_buffer_host.filled with episodes of a length windows can span: a done with probability ``p_done`` (any non-zero byte), a
+    timeout beside a third of the dones"""
+    b = filled(rng, T, B, D, A, act_dtype)
+    done = rng.random((T, B)) < p_done
+    b["done"][:] = done * rng.integers(1, 256, size=(T, B))
+    b["timeout"][:] = (done & (rng.random((T, B)) < 1.0 / 3.0)) * rng.integers(1, 256, size=(T, B))
+    return b
+
+
+def window_ids(T, B, n=N_IDS):
+    """the ids the issue names for the two ending cases: sample_ids(7, 0, T, B, n)"""
+    return rb_oracle.sample_ids(7, 0, T, B, n)
+
+
+def assert_every_ending(case, head, n_step, info):
+    """the conditions on the ORACLE's output under which no ending goes untested"""
+    T = case["T"]
+    counts = [int((info["ending"] == e).sum()) for e in (oracle.END_EPISODE, oracle.END_HEAD, oracle.END_FULL)]
+    wraps, full = int(info["wrapped"].sum()), int((info["m"] == 32).sum())
+    print("T=%d head=%d n_step=%d: endings (episode, head, n_step) %s, %d wraps, %d windows of 32" % (T, head, n_step, counts, wraps, full))
+    if case is ENDINGS:
+        assert min(counts) >= 24, counts
+        if head in (0, 4):
+            assert wraps >= 32, wraps
+    else:
+        assert full >= 12, full
+        if head in (0, 20):
+            assert wraps >= 32, wraps
+
+
+def assert_outputs(got, ref, what, keys=None):
+    for k in (keys or got):
+        assert_same_bits(got[k], np.ascontiguousarray(ref[k]).astype(got[k].dtype, copy=False), "%s %s" % (what, k))
+
+
+def some_ids(rng, N, cap=600):
+    """every id when there are few, else a random draw that keeps the first and the last id"""
+    if N <= cap:
+        return rng.permutation(N).astype(np.int64)
+    return np.concatenate([[0, N - 1], rng.integers(0, N, size=cap - 2)]).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------- the window's addresses
+def test_step_slot_both_division_widths():
+    """((t0 + k) mod T) * B + b in Python ints, for rings below and above 2^31 ids (the 32-bit and the 64-bit division of step_slot)"""
+    rng = np.random.default_rng(0)
+    for T, B in [(1, 1), (3, 63), (40, 5), (4, 4097), (2 ** 15, 2 ** 16 - 1), (2 ** 15, 2 ** 16), (2 ** 20, 2 ** 20 + 7), (7, 2 ** 40 + 1)]:
+        for s0 in [0, T * B - 1] + [int(v) for v in rng.integers(0, T * B, size=20)]:
+            for k in (0, 1, 2, 5, 31):
+                t0, b = divmod(s0, B)
+                t = (t0 + k) % T
+                assert host.step_slot(T, B, s0, k) == (t * B + b, t), (T, B, s0, k)
+
+
+# ------------------------------------------------------------------------------------------------- gather
+@pytest.mark.parametrize("D,A", DIMS)
+@pytest.mark.parametrize("T,B", SHAPES)
+def test_gather_nstep_equals_the_oracle(T, B, D, A):
+    rng = np.random.default_rng(T * 7 + B + D)
+    bufs = window_buffers(rng, T, B, D, A, 0.15, np.int32 if A == 1 else np.float32)
+    idx = some_ids(rng, T * B)
+    for n_step in N_STEPS:
+        for head in heads_of(T):
+            ref, info = oracle.gather_nstep(bufs, idx, head, n_step, 0.97)
+            assert info["bad"] == 0 and info["m"].min() >= 1 and info["m"].max() <= n_step
+            for scalar in (False, True):
+                rc, got, bad = host.sample(bufs, len(idx), head, n_step, 0.97, index=idx, force_scalar=scalar)
+                assert rc == 0 and bad == 0 and "index" not in got
+                assert_outputs(got, ref, "T=%d B=%d D=%d n_step=%d head=%d scalar=%d" % (T, B, D, n_step, head, scalar))
+            if n_step == 1:                          # the plain launch, bit for bit, whatever the head
+                rc, plain, _ = rb_host.sample(bufs, len(idx), index=idx)
+                assert_outputs({k: got[k] for k in PLAIN}, plain, "n_step == 1 against the plain gather")
+                assert (got["steps"] == 1).all() and (got["discount"] == np.float32(0.97)).all()
+
+
+@pytest.mark.parametrize("case", [ENDINGS, LONGEST], ids=["endings", "longest"])
+def test_every_ending_of_a_window(case):
+    T, B, D, A = case["T"], case["B"], 11, 3
+    bufs = window_buffers(np.random.default_rng(case["seed"]), T, B, D, A, case["p_done"])
+    idx = window_ids(T, B)
+    for n_step in case["n_steps"]:
+        for head in case["heads"]:
+            ref, info = oracle.gather_nstep(bufs, idx, head, n_step, 0.99)
+            assert_every_ending(case, head, n_step, info)
+            rc, got, bad = host.sample(bufs, len(idx), head, n_step, 0.99, index=idx)
+            assert rc == 0 and bad == 0
+            assert_outputs(got, ref, "T=%d n_step=%d head=%d" % (T, n_step, head))
+            assert np.array_equal(got["steps"], info["m"].astype(np.int32))
+            flat_next = bufs["next_obs"].reshape(T * B, D)
+            assert_same_bits(got["next_obs"], flat_next[info["last"]], "next_obs is the row of the last id")
+
+
+@pytest.mark.parametrize("gamma", [0.0, 1.0])
+def test_gamma_zero_and_one(gamma):
+    T, B, D, A = 9, 63, 11, 3
+    bufs = window_buffers(np.random.default_rng(5), T, B, D, A, 0.1)
+    idx = np.arange(T * B, dtype=np.int64)
+    ref, info = oracle.gather_nstep(bufs, idx, 4, 5, gamma)
+    rc, got, _ = host.sample(bufs, len(idx), 4, 5, gamma, index=idx)
+    assert rc == 0 and info["m"].max() == 5
+    assert_outputs(got, ref, "gamma=%g" % gamma)
+    assert (got["discount"] == np.float32(gamma)).all()
+    if gamma == 0.0:
+        assert_same_bits(got["reward"], bufs["reward"].reshape(-1)[idx], "gamma 0: the first reward alone (no reward is -0, inf or NaN)")
+
+
+# ------------------------------------------------------------------------------------------------- sample
+@pytest.mark.parametrize("T,B,D,A", [(3, 63, 11, 3), (5, 64, 4, 1), (3, 63, 376, 17), (4, 4097, 11, 3)])
+def test_sample_nstep_draws_the_ids_of_sample(T, B, D, A):
+    rng = np.random.default_rng(B + D)
+    bufs = window_buffers(rng, T, B, D, A, 0.15)
+    for size, head, n, seed, draw in ((T, T // 2, 257, 3, 0), (T, T - 1, 64, 3, 1), (1, 0, 9, 2 ** 40 + 1, 2 ** 32)):
+        ref, _ = oracle.sample_nstep(bufs, size, head, n, seed, draw, 3, 0.9)
+        assert np.array_equal(ref["index"], rb_oracle.sample_ids(seed, draw, size, B, n))
+        rc, got, bad = host.sample(bufs, n, head, 3, 0.9, size=size, seed=seed, draw=draw)
+        assert rc == 0 and bad == 0
+        assert np.array_equal(got["index"], ref["index"]) and got["index"].max() < size * B
+        assert_outputs(got, ref, "size=%d n=%d" % (size, n))
+        rc, plain, _ = rb_host.sample(bufs, n, size=size, seed=seed, draw=draw)
+        assert np.array_equal(got["index"], plain["index"])          # the ids of the plain sample launch
+
+
+def test_no_window_reads_past_the_head_of_a_ring_that_is_not_full():
+    T, B, D, A, size = 9, 63, 11, 3, 4
+    bufs = window_buffers(np.random.default_rng(9), T, B, D, A, 0.05)
+    bufs["reward"][size:] = np.nan                   # whatever a window took from the empty slots would show
+    bufs["done"][size:] = 255
+    bufs["next_obs"][size:] = np.nan
+    for n_step in (3, 5, 32):
+        ref, info = oracle.sample_nstep(bufs, size, size - 1, 500, 1, 0, n_step, 0.9)
+        rc, got, bad = host.sample(bufs, 500, size - 1, n_step, 0.9, size=size, seed=1, draw=0)
+        assert rc == 0 and bad == 0
+        assert_outputs(got, ref, "size < T, n_step=%d" % n_step)
+        assert info["last"].max() < size * B and (info["ending"] == oracle.END_HEAD).sum() > 50
+        assert np.isfinite(got["reward"]).all() and np.isfinite(got["next_obs"]).all() and (got["done"] == ref["done"]).all()
+
+
+def test_out_of_range_ids_give_zeros_and_are_counted():
+    T, B, D, A = 3, 63, 11, 3
+    rng = np.random.default_rng(1)
+    bufs = window_buffers(rng, T, B, D, A, 0.15)
+    idx = np.array([5, -1, T * B, 2 ** 62, T * B - 1, -2 ** 63, 17, 0, 188], np.int64)
+    for norm in (None, random_norm(rng, D)):
+        ref, info = oracle.gather_nstep(bufs, idx, 1, 3, 0.9, norm)
+        rc, got, bad = host.sample(bufs, len(idx), 1, 3, 0.9, index=idx, norm=norm)
+        assert rc == 0 and bad == info["bad"] == 4
+        for k in PLAIN + ("discount", "steps"):
+            assert not got[k][[1, 2, 3, 5]].any(), k
+        assert (got["steps"][[0, 4, 6, 7, 8]] >= 1).all()
+        if norm is None:
+            assert_outputs(got, ref, "out of range")
+
+
+def test_optional_outputs_are_skipped():
+    T, B, D, A = 3, 63, 11, 3
+    rng = np.random.default_rng(2)
+    bufs = window_buffers(rng, T, B, D, A, 0.15)
+    idx = rng.integers(0, T * B, size=20)
+    ref, _ = oracle.gather_nstep(bufs, idx, 2, 3, 0.9)
+    for want in (("obs",), ("next_obs", "done"), ("action", "reward"), ("reward",), ("discount",), ("steps", "next_obs"), ()):
+        rc, got, _ = host.sample(bufs, len(idx), 2, 3, 0.9, index=idx, want=want)
+        assert rc == 0 and set(got) == set(want)
+        assert_outputs(got, ref, str(want))
+
+
+def test_refused_arguments():
+    T, B, D, A = 4, 64, 11, 3
+    bufs = window_buffers(np.random.default_rng(3), T, B, D, A, 0.1)
+    idx = np.arange(8, dtype=np.int64)
+    ok = lambda **kw: host.sample(bufs, 8, **{**dict(head=1, n_step=3, gamma=0.9, index=idx), **kw})[0]
+    assert ok() == 0 and ok(n_step=1) == 0 and ok(n_step=32) == 0 and ok(gamma=0.0) == 0 and ok(gamma=1.0) == 0 and ok(head=0) == 0 and ok(head=T - 1) == 0
+    assert ok(n_step=0) == -1 and ok(n_step=33) == -1 and ok(n_step=-1) == -1
+    assert ok(gamma=-1e-9) == -1 and ok(gamma=1.0 + 1e-9) == -1 and ok(gamma=float("nan")) == -1 and ok(gamma=float("inf")) == -1
+    assert ok(head=-1) == -1 and ok(head=T) == -1
+    drawn = lambda size, head: host.sample(bufs, 8, head, 3, 0.9, size=size)[0]
+    assert drawn(T, 0) == 0 and drawn(T, T - 1) == 0 and drawn(2, 1) == 0 and drawn(1, 0) == 0
+    assert drawn(0, 0) == -1 and drawn(T + 1, 0) == -1 and drawn(2, 0) == -1 and drawn(2, 2) == -1
+
+
+# ------------------------------------------------------------------------------------------------- normalised
+@pytest.mark.parametrize("norm_obs,norm_reward", [(True, True), (True, False), (False, True)])
+@pytest.mark.parametrize("T,B,D,A", [(3, 63, 11, 3), (5, 64, 4, 1), (3, 63, 376, 17)])
+def test_normalised_outputs_within_one_ulp(T, B, D, A, norm_obs, norm_reward):
+    rng = np.random.default_rng(D + norm_obs * 2 + norm_reward)
+    bufs = window_buffers(rng, T, B, D, A, 0.15)
+    norm = random_norm(rng, D, norm_obs, norm_reward)
+    idx = rng.permutation(T * B)
+    for n_step in (1, 3):
+        ref, _ = oracle.gather_nstep(bufs, idx, T // 2, n_step, 0.95, norm)
+        raw, _ = oracle.gather_nstep(bufs, idx, T // 2, n_step, 0.95)
+        results = []
+        for scalar in (False, True):
+            rc, got, bad = host.sample(bufs, len(idx), T // 2, n_step, 0.95, index=idx, norm=norm, force_scalar=scalar)
+            assert rc == 0 and bad == 0
+            for k, clip, on in (("obs", norm["clip_obs"], norm_obs), ("next_obs", norm["clip_obs"], norm_obs), ("reward", norm["clip_reward"], norm_reward)):
+                if on:
+                    assert_f32_within_one_ulp(got[k], ref[k], clip, k)
+                else:
+                    assert_same_bits(got[k], ref[k], k + " stays raw")
+            assert_outputs(got, raw, "never normalised", keys=("action", "done", "discount", "steps"))
+            results.append(got)
+        assert_outputs(results[1], results[0], "16-byte and 4-byte paths")
+        if n_step == 1:                              # the plain normalised gather, bit for bit
+            rc, plain, _ = rb_host.sample(bufs, len(idx), index=idx, norm=norm)
+            assert_outputs({k: results[0][k] for k in PLAIN}, plain, "n_step == 1 against the plain normalised gather")
+
+
+# ------------------------------------------------------------------------------------------------- sanitizers, surface
+def test_host_functions_stay_inside_exactly_sized_buffers_under_sanitizers(tmp_path):
+    """tests/host_harness/nstep_sanitize_main.cpp: a program of its own (the sanitizer runtimes are linked into it; nothing is preloaded)"""
+    exe = str(tmp_path / "nstep_sanitize")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-o", exe, os.path.join(HARNESS, "nstep_sanitize_main.cpp")])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "T=4 B=4097 D=376 A=17" in run.stdout and "bad=3" in run.stdout
+
+
+def test_package_and_abi_declare_the_nstep_calls():
+    import random_envs_amd as rex
+    from random_envs_amd import _native
+    for name in ("rex_rbuf_gather_nstep", "rex_rbuf_sample_nstep", "rex_per_sample_nstep"):
+        assert name in _native.SYMBOLS
+    header = open(os.path.join(ROOT, "include", "rex.h")).read()
+    for name in ("rex_rbuf_gather_nstep(", "rex_rbuf_sample_nstep(", "rex_per_sample_nstep("):
+        assert name in header
+    for cls, names in ((rex.ReplayBuffer, ("sample_nstep", "gather_nstep")), (rex.PrioritizedReplayBuffer, ("sample_nstep",))):
+        for name in names:
+            assert callable(getattr(cls, name))
