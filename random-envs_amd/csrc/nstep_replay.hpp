@@ -9,9 +9,8 @@
 //                     window ends here" gives the length m as the first set bit of the half's 32 bits.  Lane i forms gamma^i while the
 //                     loads are in flight and its term gamma^i * r_i when they land; the fp64 sum then runs serially, one add per
 //                     step, over terms that are already in registers (lane reads with a wave-uniform index), every lane of the half
-//                     forming the same bits; lane 0 writes the [n] outputs.  The rows follow as in rb_sample_kernel -- whole contiguous rows,
-//                     consecutive lanes on consecutive words, the same 16-byte / 4-byte column addressing and per-pass statistics --
-//                     with obs and action taken from the first id of the window and next_obs from the last.
+//                     forming the same bits; lane 0 writes the [n] outputs.  The rows are rbuf::block_rows, the end of rb_sample_kernel
+//                     too, with obs and action taken from the first id of the window and next_obs from the last.
 // The chain of dependent global accesses is id (or none), window, rows.  Steps past the end of a window are loaded (their ids are inside
 // [0, T * B) by construction) and never looked at.  No float atomics, no grid-wide sync, no host state between launches.
 //
@@ -31,12 +30,12 @@ static_assert(HALF == 32, "a window is one bit of a 32-bit ballot half per step"
 // What a call adds to the arguments of the plain launch
 struct Win { long long head; int n_step; double gamma; };
 
-// The outputs of one launch, each optional: those of the plain launch, gamma^m and m
-struct Out { rbuf::Out base; float* discount; int32_t* steps; };
-
-VN_HD inline long long raw_id(const long long* index, uint64_t seed, uint64_t draw, long long j, long long N) {
-  return index ? index[j] : rbuf::sample_id(seed, draw, (uint64_t)j, N);
-}
+// The outputs of one launch, each optional: those of the plain launch, gamma^m and m.  Where the rows are written it is the plain set.
+struct Out {
+  rbuf::Out base; float* discount; int32_t* steps;
+  VN_HD operator const rbuf::Out&() const { return base; }
+};
+using rbuf::raw_id;
 
 // id of step k (0 <= k < 2^31) of the window that starts at s0 in [0, T * B), and its time slot.  32-bit division where every operand
 // fits (ring sizes in use are far below 2^31 ids; the 64-bit division is many times the instructions), the same values either way.
@@ -99,50 +98,27 @@ VN_HD inline Step lane_step(const Buf& b, const Tr& tr, const Win& w, int i) {
 }
 
 // The [n] outputs of sample j (raw id `raw`, behind the guard `tr`): window length m, return acc, discount g, flags of step m - 1
-VN_HD inline void lane_flat(const Out& o, const Norm& nm, long long j, long long raw, const Tr& tr, int m, double acc, double g, int last_flags) {
-  if (o.base.reward) {
+VN_HD inline void lane_flat(const Out& x, const Norm& nm, long long j, long long raw, const Tr& tr, int m, double acc, double g, int last_flags) {
+  const rbuf::Out& o = x.base;
+  if (o.reward) {
     float r = 0.0f;
     if (tr.ok) {
       r = (float)acc;
       if (nm.stats && nm.norm_reward) r = vecnorm::normalise(r, 0.0, rbuf::stat_inv_std(nm, nm.rows - 1), nm.clip_reward);
     }
-    o.base.reward[j] = r;
+    o.reward[j] = r;
   }
-  if (o.base.done) o.base.done[j] = tr.ok ? rbuf::done_out((last_flags & F_DONE) != 0, (last_flags & F_TIMEOUT) != 0) : 0.0f;
-  if (o.discount) o.discount[j] = tr.ok ? (float)g : 0.0f;
-  if (o.steps) o.steps[j] = tr.ok ? m : 0;
-  if (o.base.index) o.base.index[j] = raw;
+  if (o.done) o.done[j] = tr.ok ? rbuf::done_out((last_flags & F_DONE) != 0, (last_flags & F_TIMEOUT) != 0) : 0.0f;
+  if (x.discount) x.discount[j] = tr.ok ? (float)g : 0.0f;
+  if (x.steps) x.steps[j] = tr.ok ? m : 0;
+  if (o.index) o.index[j] = raw;
 }
 
-// A lane's share of the observation rows of sample j in the pass at c0: obs of the window's first id, next_obs of its last
-VN_HD inline void lane_obs_pass(const Buf& b, const Out& o, const Norm& nm, long long j, const Tr& first, long long last, int c0, int lane, bool vec,
-                                const double (&mean)[LANE_COLS], const double (&inv)[LANE_COLS]) {
-  const int D = b.obs_dim;
-  const size_t dst = (size_t)j * (size_t)D;
-  const bool norm = nm.stats && nm.norm_obs;
-  if (o.base.obs) {
-    const size_t src = (size_t)first.s * (size_t)D;
-    if (norm) rbuf::lane_normalise(reinterpret_cast<const float*>(b.obs + src), reinterpret_cast<float*>(o.base.obs + dst), D, c0, lane, vec, first.ok, mean, inv, nm.clip_obs);
-    else rbuf::lane_copy(b.obs + src, o.base.obs + dst, D, c0, lane, vec, first.ok);
-  }
-  if (o.base.next_obs) {
-    const size_t src = (size_t)last * (size_t)D;
-    if (norm) rbuf::lane_normalise(reinterpret_cast<const float*>(b.next_obs + src), reinterpret_cast<float*>(o.base.next_obs + dst), D, c0, lane, vec, first.ok, mean, inv, nm.clip_obs);
-    else rbuf::lane_copy(b.next_obs + src, o.base.next_obs + dst, D, c0, lane, vec, first.ok);
-  }
-}
+// The arguments of one n-step launch: those of the plain launch, the window and the two outputs it adds (s.out, discount, steps: an Out)
+struct Params { rbuf::SampleParams s; Win win; float* discount; int32_t* steps; };
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ device side
-struct Params {
-  Buf buf; Out out; Norm norm; Win win;
-  const long long* index;          // null: draw the ids (rex_rbuf_sample_nstep)
-  long long n, N;                  // samples; valid transitions (size * B) of a draw
-  unsigned long long seed, draw;
-  unsigned long long* bad;         // ids outside [0, T * B) met so far (the counter of the plain launch)
-  int vec_obs, vec_act;
-};
-
 // v of lane k of the caller's half, k the same for every lane of the wave: lane reads into scalar registers and a select, where a __shfl
 // goes through the LDS crossbar and is waited for once per step of the serial sum
 __device__ inline double half_lane(double v, int k, int half) {
@@ -158,15 +134,15 @@ __global__ __launch_bounds__(BLOCK) void rb_nstep_kernel(Params p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane / HALF, i = lane % HALF;
   const long long j0 = rbuf::wave_first(blockIdx.x, wave);
-  const int nw = rbuf::wave_count(p.n, blockIdx.x, wave);
+  const int nw = rbuf::wave_count(p.s.n, blockIdx.x, wave);
   // ---- the window: every lane of a half holds the sample's id, lane i step i
   long long raw = 0;
   Tr mine{0, false};
   if (half < nw) {
-    raw = raw_id(p.index, p.seed, p.draw, j0 + half, p.N);
-    mine = guard_id(raw, p.buf.T, p.buf.B);
+    raw = raw_id(p.s.index, p.s.seed, p.s.draw, j0 + half, p.s.N);
+    mine = guard_id(raw, p.s.buf.T, p.s.buf.B);
   }
-  const Step st = lane_step(p.buf, mine, p.win, i);
+  const Step st = lane_step(p.s.buf, mine, p.win, i);
   const unsigned long long ends = __ballot(st.end);
   const int m_half[W_SAMPLES] = {window_len((uint32_t)ends), window_len((uint32_t)(ends >> HALF))};
   const int m = half ? m_half[1] : m_half[0];
@@ -178,12 +154,12 @@ __global__ __launch_bounds__(BLOCK) void rb_nstep_kernel(Params p) {
   }
   const double g = __shfl(st.g_next, m ? m - 1 : 0, HALF);
   const int last_flags = __shfl(st.flags, m ? m - 1 : 0, HALF);
-  const long long last = mine.ok ? step_slot(p.buf.T, p.buf.B, mine.s, m - 1).s : 0;
+  const long long last = mine.ok ? step_slot(p.s.buf.T, p.s.buf.B, mine.s, m - 1).s : 0;
   if (half < nw && i == 0) {
-    lane_flat(p.out, p.norm, j0 + half, raw, mine, m, acc, g, last_flags);
-    if (!mine.ok) atomicAdd(p.bad, 1ull);
+    lane_flat(Out{p.s.out, p.discount, p.steps}, p.s.norm, j0 + half, raw, mine, m, acc, g, last_flags);
+    if (!mine.ok) atomicAdd(p.s.bad, 1ull);
   }
-  // ---- the rows: the whole wave on each of its samples in turn
+  // ---- the rows: the whole wave on each of its samples in turn, obs and action of the window's first id, next_obs of its last
   Tr tr[W_SAMPLES];
   long long end_id[W_SAMPLES];
 #pragma unroll
@@ -191,25 +167,7 @@ __global__ __launch_bounds__(BLOCK) void rb_nstep_kernel(Params p) {
     tr[k].s = __shfl(mine.s, k * HALF, 64); tr[k].ok = __shfl((int)mine.ok, k * HALF, 64) != 0;
     end_id[k] = __shfl(last, k * HALF, 64);
   }
-  if (p.out.base.action) {
-#pragma unroll
-    for (int k = 0; k < W_SAMPLES; k++)
-      if (k < nw) rbuf::lane_action(p.buf, p.out.base, j0 + k, tr[k], lane, p.vec_act);
-  }
-  const bool norm = p.norm.stats && p.norm.norm_obs;
-  if (!p.out.base.obs && !p.out.base.next_obs) return;
-  for (int c0 = 0; c0 < p.buf.obs_dim; c0 += PASS_COLS) {
-    double mean[LANE_COLS] = {0, 0, 0, 0}, inv[LANE_COLS] = {0, 0, 0, 0};
-    if (norm) {   // once per block and pass; the branch and the trip count are the same for every thread of the block
-      if (c0) __syncthreads();
-      rbuf::thread_pass_stats(p.norm, p.buf.obs_dim, c0, threadIdx.x, s_mean, s_inv);
-      __syncthreads();
-      rbuf::lane_pass_stats(s_mean, s_inv, p.buf.obs_dim, c0, lane, p.vec_obs, mean, inv);
-    }
-#pragma unroll
-    for (int k = 0; k < W_SAMPLES; k++)
-      if (k < nw) lane_obs_pass(p.buf, p.out, p.norm, j0 + k, tr[k], end_id[k], c0, lane, p.vec_obs, mean, inv);
-  }
+  rbuf::block_rows(p.s, j0, nw, tr, end_id, s_mean, s_inv);
 }
 #endif  // __HIPCC__
 

@@ -9,15 +9,18 @@
 //                     consecutive lanes on consecutive words of a transition's row.  The next_obs groups take terminal_obs on the done lanes; the blocks
 //                     of group 0 also copy the reward, done and timeout rows.
 //   rb_sample_kernel  serves rex_rbuf_sample and rex_rbuf_gather.  A block takes S_BLOCK samples, a wave W_SAMPLES of them: lane k of the wave
-//                     draws (Philox4x32-10, multiply-shift) or loads the id of the wave's k-th sample once and writes its [n] outputs; the
-//                     wave then copies each transition's obs, next_obs and action rows as whole contiguous rows, consecutive lanes on
+//                     draws (Philox4x32-10, multiply-shift) or loads the id of the wave's k-th sample once and writes its [n] outputs;
+//                     then block_rows.
+//   block_rows        the end of rb_sample_kernel and of nstep_replay.hpp's rb_nstep_kernel: the wave copies each sample's obs, next_obs
+//                     and action rows as whole contiguous rows, consecutive lanes on
 //                     consecutive words (16-byte accesses when dim % 4 == 0 and the buffers are 16-byte aligned, 4-byte ones otherwise).
 //                     Normalising: the block forms mean and 1 / sqrt(var + eps) of PASS_COLS columns once (one column per thread, through
 //                     LDS); a lane keeps those of its four columns in registers across the block's samples.
 // No float atomics, no grid-wide sync, no host state between launches; slot, fill level, seed and draw number are arguments.
 //
 // The Philox block, the id map, the next_obs select, done_out, the column addressing and the normalise calls are
-// __host__ __device__: tests/host_harness/rbuf_host.cpp drives them with g++ in grid order.
+// __host__ __device__: tests/host_harness/rbuf_host.cpp drives them with g++ in grid order (the rows through sample_walk.hpp, which follows
+// block_rows).
 #pragma once
 #include "postpass.hpp"
 #include "vecnorm.hpp"   // Norm: inv_std and normalise of the running statistics
@@ -27,7 +30,6 @@ namespace rbuf {
 using postpass::BLOCK, postpass::F4, postpass::U4, postpass::TILE_ITEMS, postpass::TILE_ROWS, postpass::row_groups, postpass::guard_id;
 using Tr = postpass::Id;               // a transition id behind the guard: never turned into an address when it is not ok
 
-constexpr int A_ENVS = TILE_ITEMS, A_ROWS = TILE_ROWS, A_STRIDE = postpass::TILE_STRIDE;   // the tile's names before postpass.hpp, for harness sources written then
 constexpr int W_SAMPLES = 2;           // samples per wave of the sample launch
 constexpr int S_BLOCK = W_SAMPLES * (BLOCK / 64);   // samples per block
 constexpr int LANE_COLS = 4;           // columns of a row a lane holds per pass: one 16-byte access, or four 4-byte ones 64 words apart
@@ -73,6 +75,11 @@ VN_HD inline uint64_t sample_bits(uint64_t seed, uint64_t draw, uint64_t j) {
 }
 // ... mapped to [0, N): the high half of u * N (bias at most N / 2^64); with replacement, a function of (seed, draw, N, j) only
 VN_HD inline long long sample_id(uint64_t seed, uint64_t draw, uint64_t j, long long N) { return (long long)mulhi64(sample_bits(seed, draw, j), (uint64_t)N); }
+
+// the raw id of sample j, for both sample kernels: loaded, or drawn when there is no index
+VN_HD inline long long raw_id(const long long* index, uint64_t seed, uint64_t draw, long long j, long long N) {
+  return index ? index[j] : sample_id(seed, draw, (uint64_t)j, N);
+}
 
 // SB3's dones * (1 - timeouts): a time-limit end still bootstraps
 VN_HD inline float done_out(uint8_t done, uint8_t timeout) { return (done && !timeout) ? 1.0f : 0.0f; }
@@ -230,26 +237,42 @@ VN_HD inline void lane_pass_stats(const double* s_mean, const double* s_inv, int
   }
 }
 
-// A lane's share of the observation rows of sample j in the pass at c0: obs and next_obs of transition `tr`
-VN_HD inline void lane_obs_pass(const Buf& b, const Out& o, const Norm& nm, long long j, const Tr& tr, int c0, int lane, bool vec,
+// A lane's share of the observation rows of sample j in the pass at c0: obs of transition `tr`, next_obs of transition `last` (the
+// same id in the plain launch, the end of the window in the n-step one; looked at only when tr.ok)
+VN_HD inline void lane_obs_pass(const Buf& b, const Out& o, const Norm& nm, long long j, const Tr& tr, long long last, int c0, int lane, bool vec,
                                 const double (&mean)[LANE_COLS], const double (&inv)[LANE_COLS]) {
   const int D = b.obs_dim;
-  const size_t src = (size_t)tr.s * (size_t)D, dst = (size_t)j * (size_t)D;
+  const size_t src = (size_t)tr.s * (size_t)D, src_next = (size_t)last * (size_t)D, dst = (size_t)j * (size_t)D;
   const bool norm = nm.stats && nm.norm_obs;
   if (o.obs) {
     if (norm) lane_normalise(reinterpret_cast<const float*>(b.obs + src), reinterpret_cast<float*>(o.obs + dst), D, c0, lane, vec, tr.ok, mean, inv, nm.clip_obs);
     else lane_copy(b.obs + src, o.obs + dst, D, c0, lane, vec, tr.ok);
   }
   if (o.next_obs) {
-    if (norm) lane_normalise(reinterpret_cast<const float*>(b.next_obs + src), reinterpret_cast<float*>(o.next_obs + dst), D, c0, lane, vec, tr.ok, mean, inv, nm.clip_obs);
-    else lane_copy(b.next_obs + src, o.next_obs + dst, D, c0, lane, vec, tr.ok);
+    if (norm) lane_normalise(reinterpret_cast<const float*>(b.next_obs + src_next), reinterpret_cast<float*>(o.next_obs + dst), D, c0, lane, vec, tr.ok, mean, inv, nm.clip_obs);
+    else lane_copy(b.next_obs + src_next, o.next_obs + dst, D, c0, lane, vec, tr.ok);
   }
+}
+// ... with both rows from one id: the plain launch's form
+VN_HD inline void lane_obs_pass(const Buf& b, const Out& o, const Norm& nm, long long j, const Tr& tr, int c0, int lane, bool vec,
+                                const double (&mean)[LANE_COLS], const double (&inv)[LANE_COLS]) {
+  lane_obs_pass(b, o, nm, j, tr, tr.s, c0, lane, vec, mean, inv);
 }
 // ... of the action row of sample j
 VN_HD inline void lane_action(const Buf& b, const Out& o, long long j, const Tr& tr, int lane, bool vec) {
   const int A = b.act_dim;
   for (int c0 = 0; c0 < A; c0 += PASS_COLS) lane_copy(b.action + (size_t)tr.s * (size_t)A, o.action + (size_t)j * (size_t)A, A, c0, lane, vec, tr.ok);
 }
+
+// The arguments of one sample / gather launch
+struct SampleParams {
+  Buf buf; Out out; Norm norm;
+  const long long* index;          // null: draw the ids (rex_rbuf_sample)
+  long long n, N;                  // samples; valid transitions (size * B) of a draw
+  unsigned long long seed, draw;
+  unsigned long long* bad;         // ids outside [0, T * B) met so far
+  int vec_obs, vec_act;
+};
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ device side
@@ -265,36 +288,17 @@ __global__ __launch_bounds__(BLOCK) void rb_add_kernel(AddParams p) {
   thread_add_write(p.buf, p.slot, tile, group, t, lds);
 }
 
-struct SampleParams {
-  Buf buf; Out out; Norm norm;
-  const long long* index;          // null: draw the ids (rex_rbuf_sample)
-  long long n, N;                  // samples; valid transitions (size * B) of a draw
-  unsigned long long seed, draw;
-  unsigned long long* bad;         // ids outside [0, T * B) met so far
-  int vec_obs, vec_act;
-};
-
-__global__ __launch_bounds__(BLOCK) void rb_sample_kernel(SampleParams p) {
-  __shared__ double s_mean[PASS_COLS], s_inv[PASS_COLS];
-  static_assert(PASS_COLS == BLOCK, "one column per thread");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long j0 = wave_first(blockIdx.x, wave);
-  const int nw = wave_count(p.n, blockIdx.x, wave);
-  Tr mine{0, false};               // lane k holds the id of the wave's k-th sample
-  if (lane < nw) {
-    const long long j = j0 + lane;
-    const long long raw = p.index ? p.index[j] : sample_id(p.seed, p.draw, (uint64_t)j, p.N);
-    mine = guard_id(raw, p.buf.T, p.buf.B);
-    lane_flat(p.buf, p.out, p.norm, j, raw, mine);
-    if (!mine.ok) atomicAdd(p.bad, 1ull);
-  }
-  Tr tr[W_SAMPLES];
-#pragma unroll
-  for (int k = 0; k < W_SAMPLES; k++) { tr[k].s = __shfl(mine.s, k, 64); tr[k].ok = __shfl((int)mine.ok, k, 64) != 0; }
+// The rows of a block's samples, the end of both sample kernels: the action rows, then the observation rows pass by pass with the
+// block's statistics through the caller's two LDS arrays.  The wave's k-th sample (nw of them, the first is sample j0) takes obs and
+// action from first[k] and next_obs from last[k].  Every thread of the block calls it (it holds __syncthreads).  `p` BY VALUE: handed
+// the kernel's argument by reference the same lines compile to 89 VGPRs in rb_sample_kernel, by value to 83 (profiles/HISTORY.md).
+__device__ inline void block_rows(const SampleParams p, long long j0, int nw, const Tr (&first)[W_SAMPLES], const long long (&last)[W_SAMPLES],
+                                  double* s_mean, double* s_inv) {
+  const int lane = threadIdx.x & 63;
   if (p.out.action) {
 #pragma unroll
     for (int k = 0; k < W_SAMPLES; k++)
-      if (k < nw) lane_action(p.buf, p.out, j0 + k, tr[k], lane, p.vec_act);
+      if (k < nw) lane_action(p.buf, p.out, j0 + k, first[k], lane, p.vec_act);
   }
   const bool norm = p.norm.stats && p.norm.norm_obs;
   if (!p.out.obs && !p.out.next_obs) return;
@@ -308,8 +312,29 @@ __global__ __launch_bounds__(BLOCK) void rb_sample_kernel(SampleParams p) {
     }
 #pragma unroll
     for (int k = 0; k < W_SAMPLES; k++)
-      if (k < nw) lane_obs_pass(p.buf, p.out, p.norm, j0 + k, tr[k], c0, lane, p.vec_obs, mean, inv);
+      if (k < nw) lane_obs_pass(p.buf, p.out, p.norm, j0 + k, first[k], last[k], c0, lane, p.vec_obs, mean, inv);
   }
+}
+
+__global__ __launch_bounds__(BLOCK) void rb_sample_kernel(SampleParams p) {
+  __shared__ double s_mean[PASS_COLS], s_inv[PASS_COLS];
+  static_assert(PASS_COLS == BLOCK, "one column per thread");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long j0 = wave_first(blockIdx.x, wave);
+  const int nw = wave_count(p.n, blockIdx.x, wave);
+  Tr mine{0, false};               // lane k holds the id of the wave's k-th sample
+  if (lane < nw) {
+    const long long j = j0 + lane;
+    const long long raw = raw_id(p.index, p.seed, p.draw, j, p.N);
+    mine = guard_id(raw, p.buf.T, p.buf.B);
+    lane_flat(p.buf, p.out, p.norm, j, raw, mine);
+    if (!mine.ok) atomicAdd(p.bad, 1ull);
+  }
+  Tr tr[W_SAMPLES];
+  long long last[W_SAMPLES];
+#pragma unroll
+  for (int k = 0; k < W_SAMPLES; k++) { tr[k].s = __shfl(mine.s, k, 64); tr[k].ok = __shfl((int)mine.ok, k, 64) != 0; last[k] = tr[k].s; }
+  block_rows(p, j0, nw, tr, last, s_mean, s_inv);
 }
 #endif  // __HIPCC__
 

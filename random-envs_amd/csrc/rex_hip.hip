@@ -4,7 +4,8 @@
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
 // math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp (the last also owns the pair kernel's view of the SoA state: load_lane /
 // store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp, replay_buffer.hpp and eplog.hpp over
-// postpass.hpp (their common block, chunk walk, LDS tile and id guard).  Profiling probes
+// postpass.hpp (their common block, chunk walk, LDS tile and id guard); priority_replay.hpp draws ids for replay_buffer.hpp's sample launch and
+// nstep_replay.hpp puts a window in front of that launch's rows (one rbuf::SampleParams, one block_rows, one launch_sample here).  Profiling probes
 // live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.
@@ -1249,12 +1250,17 @@ extern "C" int rex_eplog_set_lane_state(rex_t* h, const double* ep_return, const
 // ------------------------------------------------------------------------------------------
 // off-policy replay buffer (replay_buffer.hpp): fused transposing add and on-device sampling over caller-owned transition-major buffers
 // ------------------------------------------------------------------------------------------
+// allocate once, synchronise, zero: the n device counters an opt-in layer keeps on the handle
+static int enable_counters(void** mem, int n) {
+  if (!*mem) HIP_TRY(hipMalloc(mem, sizeof(unsigned long long) * n));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemset(*mem, 0, sizeof(unsigned long long) * n));
+  return REX_OK;
+}
+
 extern "C" int rex_rbuf_enable(rex_t* h) {
   REX_ENTER(h, "rex_rbuf_enable");
-  if (!h->rbuf_mem) HIP_TRY(hipMalloc(&h->rbuf_mem, sizeof(unsigned long long)));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemset(h->rbuf_mem, 0, sizeof(unsigned long long)));
-  return REX_OK;
+  return enable_counters(&h->rbuf_mem, 1);
 }
 
 // the caller's struct with the handle's sizes; every buffer is required
@@ -1286,23 +1292,45 @@ extern "C" int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, co
   return REX_OK;
 }
 
-// the one launch behind rex_rbuf_sample (index == nullptr: the ids are drawn) and rex_rbuf_gather
-static int launch_rbuf_sample(const rex_env* h, const char* fn, rbuf::SampleParams p, int normalise, hipStream_t st) {
+// The one launch path of the sample family -- rex_rbuf_sample / _gather / rex_per_sample through rb_sample_kernel, their _nstep forms
+// through rb_nstep_kernel: `p` is what the kernel takes, `s` the rbuf::SampleParams inside it (p itself for the plain kernel)
+template <class P>
+static int launch_sample(const rex_env* h, const char* fn, void (*kernel)(P), P& p, rbuf::SampleParams& s, int normalise, void* stream) {
   if (normalise) {
     if (!h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
     const rex_norm_config& c = h->norm_cfg;
-    p.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
+    s.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
   }
-  if (p.n == 0) return REX_OK;
-  const long long blocks = rbuf::sample_blocks(p.n);
-  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
+  if (s.n == 0) return REX_OK;
+  const long long blocks = rbuf::sample_blocks(s.n);
+  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, s.n);
   // 16-byte accesses: with dim a multiple of 4 every row of a 16-byte aligned buffer starts 16-byte aligned
-  const rbuf::Buf& b = p.buf;
-  p.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, p.out.obs, p.out.next_obs)) ? 1 : 0;
-  p.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, p.out.action)) ? 1 : 0;
-  p.bad = (unsigned long long*)h->rbuf_mem;
-  hipLaunchKernelGGL(rbuf::rb_sample_kernel, dim3((unsigned)blocks), dim3(rbuf::BLOCK), 0, st, p);
+  const rbuf::Buf& b = s.buf;
+  s.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, s.out.obs, s.out.next_obs)) ? 1 : 0;
+  s.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, s.out.action)) ? 1 : 0;
+  s.bad = (unsigned long long*)h->rbuf_mem;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(rbuf::BLOCK), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+
+// the caller's output pointers as the kernels take them (index_out null for a gather: the caller has the ids)
+static rbuf::Out rbuf_out(float* obs, float* next_obs, void* action, float* reward, float* done, int64_t* index) {
+  return rbuf::Out{(uint32_t*)obs, (uint32_t*)next_obs, (uint32_t*)action, reward, done, (long long*)index};
+}
+
+// The arguments of a draw: `size` filled slots of T, then n samples (an n-step call has its rule for a ring that is not full between the two)
+static int check_size(const char* fn, int64_t size, int64_t T) {
+  if (size < 1 || size > T) return set_err(REX_ERR_ARG, "%s: size %lld outside [1, %lld]", fn, (long long)size, (long long)T);
+  return REX_OK;
+}
+static int check_n(const char* fn, int64_t n) {
+  if (n < 0) return set_err(REX_ERR_ARG, "%s: n must be >= 0", fn);
+  return REX_OK;
+}
+// ... of a gather
+static int check_gather(const char* fn, const int64_t* index, int64_t n) {
+  if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "%s: n must be >= 0 and index given", fn);
   return REX_OK;
 }
 
@@ -1313,11 +1341,11 @@ extern "C" int rex_rbuf_sample(rex_t* h, const rex_rbuf_buffers* buf, int64_t si
   REX_NEEDS(h, rbuf_mem, "rex_rbuf_sample", "rex_rbuf_enable");
   rbuf::SampleParams p{};
   if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample", &p.buf)) return rc;
-  if (size < 1 || size > buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_sample: size %lld outside [1, %lld]", (long long)size, (long long)buf->T);
-  if (n < 0) return set_err(REX_ERR_ARG, "rex_rbuf_sample: n must be >= 0");
-  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, (long long*)index_out};
+  if (int rc = check_size("rex_rbuf_sample", size, buf->T)) return rc;
+  if (int rc = check_n("rex_rbuf_sample", n)) return rc;
+  p.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, index_out);
   p.n = n; p.N = (long long)size * h->B; p.seed = seed; p.draw = draw;
-  return launch_rbuf_sample(h, "rex_rbuf_sample", p, normalise, (hipStream_t)stream);
+  return launch_sample(h, "rex_rbuf_sample", rbuf::rb_sample_kernel, p, p, normalise, stream);
 }
 
 extern "C" int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int normalise, float* obs_out,
@@ -1326,10 +1354,10 @@ extern "C" int rex_rbuf_gather(rex_t* h, const rex_rbuf_buffers* buf, const int6
   REX_NEEDS(h, rbuf_mem, "rex_rbuf_gather", "rex_rbuf_enable");
   rbuf::SampleParams p{};
   if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather", &p.buf)) return rc;
-  if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rbuf_gather: n must be >= 0 and index given");
-  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr};
+  if (int rc = check_gather("rex_rbuf_gather", index, n)) return rc;
+  p.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, nullptr);
   p.index = (const long long*)index; p.n = n; p.N = p.buf.T * p.buf.B;
-  return launch_rbuf_sample(h, "rex_rbuf_gather", p, normalise, (hipStream_t)stream);
+  return launch_sample(h, "rex_rbuf_gather", rbuf::rb_sample_kernel, p, p, normalise, stream);
 }
 
 extern "C" int rex_rbuf_read_bad_indices(rex_t* h, int64_t* out, int clear) {
@@ -1351,10 +1379,7 @@ extern "C" int64_t rex_per_tree_len(int64_t N) {
 
 extern "C" int rex_per_enable(rex_t* h) {
   REX_ENTER(h, "rex_per_enable");
-  if (!h->per_mem) HIP_TRY(hipMalloc(&h->per_mem, sizeof(unsigned long long) * per::N_COUNTERS));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemset(h->per_mem, 0, sizeof(unsigned long long) * per::N_COUNTERS));
-  return REX_OK;
+  return enable_counters(&h->per_mem, per::N_COUNTERS);
 }
 
 // the caller's struct with the handle's batch and the tree's shape; every buffer is required
@@ -1453,6 +1478,23 @@ extern "C" int rex_per_draw(rex_t* h, const rex_per_buffers* buf, int64_t n, uin
   return launch_per_draw("rex_per_draw", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream);
 }
 
+// What rex_per_sample and rex_per_sample_nstep do ahead of their gather, in two parts (an n-step call checks its window between them): both
+// descriptions and their agreement on T ...
+static int per_pair(const rex_env* h, const char* fn, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, per::Buf* b, rbuf::Buf* out) {
+  if (int rc = per_buf(h, buf, fn, b)) return rc;
+  if (int rc = rbuf_buf(h, rb, fn, out)) return rc;
+  if (rb->T != buf->T) return set_err(REX_ERR_ARG, "%s: the two descriptions disagree on T (%lld and %lld)", fn, (long long)rb->T, (long long)buf->T);
+  return REX_OK;
+}
+// ... then the normalise state BEFORE the draw is enqueued, and the draw, whose ids become the gather's
+static int per_draw_ids(const rex_env* h, const char* fn, const per::Buf& b, int64_t n, uint64_t seed, uint64_t draw, int normalise, int64_t* index_out,
+                        float* prob_out, void* stream, rbuf::SampleParams* p) {
+  if (normalise && !h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
+  if (int rc = launch_per_draw(fn, b, n, seed, draw, index_out, prob_out, (hipStream_t)stream)) return rc;
+  p->index = (const long long*)index_out; p->n = n; p->N = p->buf.T * p->buf.B;
+  return REX_OK;
+}
+
 extern "C" int rex_per_sample(rex_t* h, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, int64_t n, uint64_t seed, uint64_t draw,
                               int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
                               int64_t* index_out, float* prob_out, void* stream) {
@@ -1461,14 +1503,10 @@ extern "C" int rex_per_sample(rex_t* h, const rex_rbuf_buffers* rb, const rex_pe
   REX_NEEDS(h, rbuf_mem, "rex_per_sample", "rex_rbuf_enable");
   per::Buf b;
   rbuf::SampleParams p{};
-  if (int rc = per_buf(h, buf, "rex_per_sample", &b)) return rc;
-  if (int rc = rbuf_buf(h, rb, "rex_per_sample", &p.buf)) return rc;
-  if (rb->T != buf->T) return set_err(REX_ERR_ARG, "rex_per_sample: the two descriptions disagree on T (%lld and %lld)", (long long)rb->T, (long long)buf->T);
-  if (normalise && !h->norm_mem) return set_err(REX_ERR_STATE, "rex_per_sample: normalise needs rex_norm_enable on this handle");
-  if (int rc = launch_per_draw("rex_per_sample", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream)) return rc;
-  p.out = rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr};
-  p.index = (const long long*)index_out; p.n = n; p.N = p.buf.T * p.buf.B;
-  return launch_rbuf_sample(h, "rex_per_sample", p, normalise, (hipStream_t)stream);
+  if (int rc = per_pair(h, "rex_per_sample", rb, buf, &b, &p.buf)) return rc;
+  if (int rc = per_draw_ids(h, "rex_per_sample", b, n, seed, draw, normalise, index_out, prob_out, stream, &p)) return rc;
+  p.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, nullptr);
+  return launch_sample(h, "rex_per_sample", rbuf::rb_sample_kernel, p, p, normalise, stream);
 }
 
 extern "C" int rex_per_read_counters(rex_t* h, int64_t* out, int clear) {
@@ -1495,38 +1533,19 @@ static int nstep_win(const char* fn, const rbuf::Buf& b, int64_t head, int n_ste
   return REX_OK;
 }
 
-// the one launch behind rex_rbuf_sample_nstep (index == nullptr: the ids are drawn), rex_rbuf_gather_nstep and rex_per_sample_nstep
-static int launch_rbuf_nstep(const rex_env* h, const char* fn, nstep::Params p, int normalise, hipStream_t st) {
-  if (normalise) {
-    if (!h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
-    const rex_norm_config& c = h->norm_cfg;
-    p.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
-  }
-  if (p.n == 0) return REX_OK;
-  const long long blocks = rbuf::sample_blocks(p.n);
-  if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, p.n);
-  const rbuf::Buf& b = p.buf;
-  const rbuf::Out& o = p.out.base;
-  p.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, o.obs, o.next_obs)) ? 1 : 0;
-  p.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, o.action)) ? 1 : 0;
-  p.bad = (unsigned long long*)h->rbuf_mem;
-  hipLaunchKernelGGL(nstep::rb_nstep_kernel, dim3((unsigned)blocks), dim3(nstep::BLOCK), 0, st, p);
-  HIP_TRY(hipGetLastError());
-  return REX_OK;
-}
-
 extern "C" int rex_rbuf_gather_nstep(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int64_t head, int n_step, double gamma,
                                      int normalise, float* obs_out, float* next_obs_out, void* action_out, float* reward_out, float* done_out,
                                      float* discount_out, int32_t* steps_out, void* stream) {
   REX_ENTER(h, "rex_rbuf_gather_nstep");
   REX_NEEDS(h, rbuf_mem, "rex_rbuf_gather_nstep", "rex_rbuf_enable");
   nstep::Params p{};
-  if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather_nstep", &p.buf)) return rc;
-  if (int rc = nstep_win("rex_rbuf_gather_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
-  if (n < 0 || (n > 0 && !index)) return set_err(REX_ERR_ARG, "rex_rbuf_gather_nstep: n must be >= 0 and index given");
-  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr}, discount_out, steps_out};
-  p.index = (const long long*)index; p.n = n; p.N = p.buf.T * p.buf.B;
-  return launch_rbuf_nstep(h, "rex_rbuf_gather_nstep", p, normalise, (hipStream_t)stream);
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather_nstep", &p.s.buf)) return rc;
+  if (int rc = nstep_win("rex_rbuf_gather_nstep", p.s.buf, head, n_step, gamma, &p.win)) return rc;
+  if (int rc = check_gather("rex_rbuf_gather_nstep", index, n)) return rc;
+  p.s.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, nullptr);
+  p.discount = discount_out; p.steps = steps_out;
+  p.s.index = (const long long*)index; p.s.n = n; p.s.N = p.s.buf.T * p.s.buf.B;
+  return launch_sample(h, "rex_rbuf_gather_nstep", nstep::rb_nstep_kernel, p, p.s, normalise, stream);
 }
 
 extern "C" int rex_rbuf_sample_nstep(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t head, int64_t n, uint64_t seed, uint64_t draw,
@@ -1535,17 +1554,17 @@ extern "C" int rex_rbuf_sample_nstep(rex_t* h, const rex_rbuf_buffers* buf, int6
   REX_ENTER(h, "rex_rbuf_sample_nstep");
   REX_NEEDS(h, rbuf_mem, "rex_rbuf_sample_nstep", "rex_rbuf_enable");
   nstep::Params p{};
-  if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample_nstep", &p.buf)) return rc;
-  if (int rc = nstep_win("rex_rbuf_sample_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
-  if (size < 1 || size > buf->T) return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: size %lld outside [1, %lld]", (long long)size, (long long)buf->T);
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample_nstep", &p.s.buf)) return rc;
+  if (int rc = nstep_win("rex_rbuf_sample_nstep", p.s.buf, head, n_step, gamma, &p.win)) return rc;
+  if (int rc = check_size("rex_rbuf_sample_nstep", size, buf->T)) return rc;
   if (size < buf->T && head != size - 1)
     return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: a ring that is not full (size %lld < %lld) has head == size - 1, not %lld", (long long)size,
                    (long long)buf->T, (long long)head);
-  if (n < 0) return set_err(REX_ERR_ARG, "rex_rbuf_sample_nstep: n must be >= 0");
-  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, (long long*)index_out}, discount_out,
-                     steps_out};
-  p.n = n; p.N = (long long)size * h->B; p.seed = seed; p.draw = draw;
-  return launch_rbuf_nstep(h, "rex_rbuf_sample_nstep", p, normalise, (hipStream_t)stream);
+  if (int rc = check_n("rex_rbuf_sample_nstep", n)) return rc;
+  p.s.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, index_out);
+  p.discount = discount_out; p.steps = steps_out;
+  p.s.n = n; p.s.N = (long long)size * h->B; p.s.seed = seed; p.s.draw = draw;
+  return launch_sample(h, "rex_rbuf_sample_nstep", nstep::rb_nstep_kernel, p, p.s, normalise, stream);
 }
 
 extern "C" int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, int64_t n, int64_t head, uint64_t seed, uint64_t draw,
@@ -1556,14 +1575,10 @@ extern "C" int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rb, const 
   REX_NEEDS(h, rbuf_mem, "rex_per_sample_nstep", "rex_rbuf_enable");
   per::Buf b;
   nstep::Params p{};
-  if (int rc = per_buf(h, buf, "rex_per_sample_nstep", &b)) return rc;
-  if (int rc = rbuf_buf(h, rb, "rex_per_sample_nstep", &p.buf)) return rc;
-  if (rb->T != buf->T)
-    return set_err(REX_ERR_ARG, "rex_per_sample_nstep: the two descriptions disagree on T (%lld and %lld)", (long long)rb->T, (long long)buf->T);
-  if (int rc = nstep_win("rex_per_sample_nstep", p.buf, head, n_step, gamma, &p.win)) return rc;
-  if (normalise && !h->norm_mem) return set_err(REX_ERR_STATE, "rex_per_sample_nstep: normalise needs rex_norm_enable on this handle");
-  if (int rc = launch_per_draw("rex_per_sample_nstep", b, n, seed, draw, index_out, prob_out, (hipStream_t)stream)) return rc;
-  p.out = nstep::Out{rbuf::Out{(uint32_t*)obs_out, (uint32_t*)next_obs_out, (uint32_t*)action_out, reward_out, done_out, nullptr}, discount_out, steps_out};
-  p.index = (const long long*)index_out; p.n = n; p.N = p.buf.T * p.buf.B;
-  return launch_rbuf_nstep(h, "rex_per_sample_nstep", p, normalise, (hipStream_t)stream);
+  if (int rc = per_pair(h, "rex_per_sample_nstep", rb, buf, &b, &p.s.buf)) return rc;
+  if (int rc = nstep_win("rex_per_sample_nstep", p.s.buf, head, n_step, gamma, &p.win)) return rc;
+  if (int rc = per_draw_ids(h, "rex_per_sample_nstep", b, n, seed, draw, normalise, index_out, prob_out, stream, &p.s)) return rc;
+  p.s.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, nullptr);
+  p.discount = discount_out; p.steps = steps_out;
+  return launch_sample(h, "rex_per_sample_nstep", nstep::rb_nstep_kernel, p, p.s, normalise, stream);
 }

@@ -49,15 +49,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         minibatch.  The ids are a function of (seed, number of the draw, batch_size, j) and the priorities."""
         if len(self) == 0:
             raise RuntimeError("PrioritizedReplayBuffer.sample: the buffer is empty")
-        t = self._torch
-        n = int(batch_size)
-        out = self._outputs(n, True)
-        out["prob"] = t.empty(n, dtype=t.float32, device=self.device)
-        _native.check(self._L.rex_per_sample(self._h, ctypes.byref(self._desc), ctypes.byref(self._per), n, self.seed, self.draws,
-                                             self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]),
-                                             self._p(out["reward"]), self._p(out["done"]), self._p(out["index"]), self._p(out["prob"]), self._stream()))
-        self.draws += 1
-        return self._with_weight(out, beta)
+        return self._with_weight(self._launch(int(batch_size), None, None, normalize, ctypes.byref(self._per)), beta)
 
     def _with_weight(self, out, beta):
         t = self._torch
@@ -73,17 +65,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         of :meth:`sample` plus ``discount`` and ``steps``."""
         if len(self) == 0:
             raise RuntimeError("PrioritizedReplayBuffer.sample_nstep: the buffer is empty")
-        t = self._torch
-        n = int(batch_size)
-        out = self._nstep_outputs(n, True)
-        out["prob"] = t.empty(n, dtype=t.float32, device=self.device)
-        _native.check(self._L.rex_per_sample_nstep(self._h, ctypes.byref(self._desc), ctypes.byref(self._per), n, self._head(), self.seed, self.draws,
-                                                   int(n_step), float(gamma), self._normalise_flag(normalize), self._p(out["obs"]),
-                                                   self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]),
-                                                   self._p(out["discount"]), self._p(out["steps"]), self._p(out["index"]), self._p(out["prob"]),
-                                                   self._stream()))
-        self.draws += 1
-        return self._with_weight(out, beta)
+        return self._with_weight(self._launch(int(batch_size), None, (n_step, gamma), normalize, ctypes.byref(self._per)), beta)
 
     def update_priorities(self, index, td_error):
         """Priority of transition ``index[j]`` <- ``(|td_error[j]| + eps) ** alpha`` (float32, computed by torch: a device ``powf`` would

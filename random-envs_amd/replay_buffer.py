@@ -73,13 +73,46 @@ class ReplayBuffer(Layer):
             self.pos, self.full = 0, True
 
     # ------------------------------------------------------------------ learn
-    def _outputs(self, n, with_index):
-        t = self._torch
-        f32 = dict(dtype=t.float32, device=self.device)
-        out = dict(obs=t.empty(n, self.obs_dim, **f32), next_obs=t.empty(n, self.obs_dim, **f32),
-                   action=t.empty(n, self.act_dim, dtype=self.action.dtype, device=self.device), reward=t.empty(n, **f32), done=t.empty(n, **f32))
-        if with_index:
-            out["index"] = t.empty(n, dtype=t.int64, device=self.device)
+    def _launch(self, n, index, nstep, normalize, per=None):
+        """The one call site of the sample family.  ``index`` None: the ids are drawn (``draws`` goes up), uniformly, or by the priorities
+        behind ``per`` (a :class:`PrioritizedReplayBuffer`'s description, by reference); else they are gathered.  ``nstep``: None or
+        ``(n_step, gamma)``.  Allocates and returns the output dict.  The five pointers every entry point takes are formed once; each call
+        below names the entry point's own extra outputs beside them, in the order of include/rex.h."""
+        t, dev, p, L = self._torch, self.device, self._p, self._L
+        f32 = t.float32
+        obs, nxt = t.empty(n, self.obs_dim, dtype=f32, device=dev), t.empty(n, self.obs_dim, dtype=f32, device=dev)
+        act = t.empty(n, self.act_dim, dtype=self.action.dtype, device=dev)
+        rew, done = t.empty(n, dtype=f32, device=dev), t.empty(n, dtype=f32, device=dev)
+        out = {"obs": obs, "next_obs": nxt, "action": act, "reward": rew, "done": done}
+        five = (p(obs), p(nxt), p(act), p(rew), p(done))
+        h, desc, norm, stream = self._h, ctypes.byref(self._desc), self._normalise_flag(normalize), self._stream()
+        if index is None:
+            ids = out["index"] = t.empty(n, dtype=t.int64, device=dev)
+            size, seed, draw = self.n_slots if self.full else self.pos, self.seed, self.draws
+            if per is not None:
+                prob = out["prob"] = t.empty(n, dtype=f32, device=dev)
+        if nstep is None:
+            if index is not None:
+                rc = L.rex_rbuf_gather(h, desc, p(index), n, norm, *five, stream)
+            elif per is None:
+                rc = L.rex_rbuf_sample(h, desc, size, n, seed, draw, norm, *five, p(ids), stream)
+            else:
+                rc = L.rex_per_sample(h, desc, per, n, seed, draw, norm, *five, p(ids), p(prob), stream)
+        else:
+            head, n_step, gamma = self._head(), int(nstep[0]), float(nstep[1])
+            disc = out["discount"] = t.empty(n, dtype=f32, device=dev)
+            steps = out["steps"] = t.empty(n, dtype=t.int32, device=dev)
+            if index is not None:
+                rc = L.rex_rbuf_gather_nstep(h, desc, p(index), n, head, n_step, gamma, norm, *five, p(disc), p(steps), stream)
+            elif per is None:
+                rc = L.rex_rbuf_sample_nstep(h, desc, size, head, n, seed, draw, n_step, gamma, norm, *five, p(disc), p(steps), p(ids), stream)
+            else:
+                rc = L.rex_per_sample_nstep(h, desc, per, n, head, seed, draw, n_step, gamma, norm, *five, p(disc), p(steps), p(ids), p(prob), stream)
+        _native.check(rc)
+        if index is None:
+            self.draws += 1
+        else:
+            out["index"] = index
         return out
 
     def sample(self, batch_size, normalize=None):
@@ -89,40 +122,20 @@ class ReplayBuffer(Layer):
         a function of (seed, number of the draw, fill level, batch, j).  ``normalize=None`` means "yes iff the env is a
         ``NormalizedVecRandomEnv``": observations and rewards then come back normalised with its running statistics as
         they stand."""
-        size = self.n_slots if self.full else self.pos
-        if size == 0:
+        if self.pos == 0 and not self.full:
             raise RuntimeError("ReplayBuffer.sample: the buffer is empty")
-        n = int(batch_size)
-        out = self._outputs(n, True)
-        _native.check(self._L.rex_rbuf_sample(self._h, ctypes.byref(self._desc), size, n, self.seed, self.draws, self._normalise_flag(normalize),
-                                              self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]),
-                                              self._p(out["done"]), self._p(out["index"]), self._stream()))
-        self.draws += 1
-        return out
+        return self._launch(int(batch_size), None, None, normalize)
 
     def gather(self, index, normalize=None):
         """The same launch for the caller's ids ``index`` (int64 on the device): prioritised schemes, tests.  An id outside
         ``[0, n_slots * batch)`` gives zeros and is counted (:meth:`bad_indices`)."""
         self._check_index(index)
-        n = index.numel()
-        out = self._outputs(n, False)
-        _native.check(self._L.rex_rbuf_gather(self._h, ctypes.byref(self._desc), self._p(index), n, self._normalise_flag(normalize),
-                                              self._p(out["obs"]), self._p(out["next_obs"]), self._p(out["action"]), self._p(out["reward"]),
-                                              self._p(out["done"]), self._stream()))
-        out["index"] = index
-        return out
+        return self._launch(index.numel(), index, None, normalize)
 
     # ------------------------------------------------------------------ learn, n-step
     def _head(self):
         """The slot written most recently: where every n-step window stops at the latest."""
         return (self.pos - 1) % self.n_slots
-
-    def _nstep_outputs(self, n, with_index):
-        t = self._torch
-        out = self._outputs(n, with_index)
-        out["discount"] = t.empty(n, dtype=t.float32, device=self.device)
-        out["steps"] = t.empty(n, dtype=t.int32, device=self.device)
-        return out
 
     def sample_nstep(self, batch_size, n_step, gamma, normalize=None):
         """:meth:`sample` with an n-step return behind every id, still in ONE launch: the window of transition ``s`` follows its env
@@ -131,30 +144,15 @@ class ReplayBuffer(Layer):
         gamma^(m-1) r_(m-1)`` (fp64 sum, one rounding), ``discount`` [n] float32 is ``gamma^m`` -- what the target value is multiplied
         by -- and ``steps`` [n] int32 is ``m``.  The ids are those :meth:`sample` draws at the same draw number, and the two methods
         share that number.  With ``normalize`` the return is normalised once, as a reward is."""
-        size = self.n_slots if self.full else self.pos
-        if size == 0:
+        if self.pos == 0 and not self.full:
             raise RuntimeError("ReplayBuffer.sample_nstep: the buffer is empty")
-        n = int(batch_size)
-        out = self._nstep_outputs(n, True)
-        _native.check(self._L.rex_rbuf_sample_nstep(self._h, ctypes.byref(self._desc), size, self._head(), n, self.seed, self.draws, int(n_step),
-                                                    float(gamma), self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]),
-                                                    self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]), self._p(out["discount"]),
-                                                    self._p(out["steps"]), self._p(out["index"]), self._stream()))
-        self.draws += 1
-        return out
+        return self._launch(int(batch_size), None, (n_step, gamma), normalize)
 
     def gather_nstep(self, index, n_step, gamma, normalize=None):
         """The same launch for the caller's ids, as :meth:`gather` is to :meth:`sample`.  An id out of range gives zeros (``discount``
         and ``steps`` included) and is counted (:meth:`bad_indices`)."""
         self._check_index(index)
-        n = index.numel()
-        out = self._nstep_outputs(n, False)
-        _native.check(self._L.rex_rbuf_gather_nstep(self._h, ctypes.byref(self._desc), self._p(index), n, self._head(), int(n_step), float(gamma),
-                                                    self._normalise_flag(normalize), self._p(out["obs"]), self._p(out["next_obs"]),
-                                                    self._p(out["action"]), self._p(out["reward"]), self._p(out["done"]), self._p(out["discount"]),
-                                                    self._p(out["steps"]), self._stream()))
-        out["index"] = index
-        return out
+        return self._launch(index.numel(), index, (n_step, gamma), normalize)
 
     def bad_indices(self, clear=True):
         """Ids out of range the gathers met since the last clearing read (their outputs are zeros).  Synchronises."""

@@ -4,20 +4,11 @@
 // of the lanes' arrays, the per-pass statistics as arrays -- so the CPU tests hold the kernel's arithmetic and addressing to the oracle for any
 // size without a GPU.
 #include <cstdint>
-#include <vector>
 
 #include "../../random-envs_amd/csrc/nstep_replay.hpp"
+#include "sample_walk.hpp"
 
 using namespace nstep;
-
-namespace {
-
-// bufs: obs, next_obs, action, reward, done, timeout
-Buf make_buf(void** p, long long T, long long B, int obs_dim, int act_dim) {
-  return Buf{(uint32_t*)p[0], (uint32_t*)p[1], (uint32_t*)p[2], (float*)p[3], (uint8_t*)p[4], (uint8_t*)p[5], T, B, obs_dim, act_dim};
-}
-
-}  // namespace
 
 // id and time slot of step k of the window at s0 (both division widths of step_slot are reachable from here)
 extern "C" void ns_host_step_slot(long long T, long long B, long long s0, int k, long long* s, long long* t) {
@@ -25,29 +16,21 @@ extern "C" void ns_host_step_slot(long long T, long long B, long long s0, int k,
   *s = at.s; *t = at.t;
 }
 
-// outs: obs [n][obs_dim], next_obs [n][obs_dim], action [n][act_dim], reward, done [n] f32, index [n] int64, discount [n] f32, steps [n] int32
-// (each may be null).  index == null: the ids are drawn over size * B transitions.  stats == null: no normalisation.  force_scalar != 0: the
-// 4-byte path even where 16-byte accesses are allowed.  Returns -1 for the arguments the C-ABI refuses.
+// The n-step launch: the arguments of sample_walk::make_params with the window's, outs[6] discount [n] f32 and outs[7] steps [n] int32 (each may
+// be null).  Returns -1 for the arguments the C-ABI refuses.
 extern "C" int ns_host_sample(void** bufs, long long T, long long B, int obs_dim, int act_dim, const long long* index, long long n, long long size,
                               long long head, unsigned long long seed, unsigned long long draw, int n_step, double gamma, void** outs,
                               const double* stats, int norm_obs, int norm_reward, double eps, double clip_obs, double clip_reward, int force_scalar,
                               long long* bad) {
-  const Buf b = make_buf(bufs, T, B, obs_dim, act_dim);
   if (n_step < 1 || n_step > MAX_STEPS || !(gamma >= 0.0 && gamma <= 1.0) || head < 0 || head >= T) return -1;
   if (!index && (size < 1 || size > T || (size < T && head != size - 1))) return -1;
   if (n < 0) return -1;
-  const Out o{rbuf::Out{(uint32_t*)outs[0], (uint32_t*)outs[1], (uint32_t*)outs[2], (float*)outs[3], (float*)outs[4], (long long*)outs[5]}, (float*)outs[6],
-              (int32_t*)outs[7]};
-  const Norm nm{stats, obs_dim + 1, norm_obs, norm_reward, eps, clip_obs, clip_reward};
-  const Win w{head, n_step, gamma};
-  const long long N = index ? T * B : size * B;
-  const bool vec_obs = !force_scalar && obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, o.base.obs, o.base.next_obs);
-  const bool vec_act = !force_scalar && act_dim % 4 == 0 && postpass::all_aligned16(b.action, o.base.action);
-  const bool norm = nm.stats && nm.norm_obs;
-  double s_mean[PASS_COLS], s_inv[PASS_COLS];
+  const Params p{sample_walk::make_params(bufs, T, B, obs_dim, act_dim, index, n, size, seed, draw, outs, stats, norm_obs, norm_reward, eps, clip_obs,
+                                          clip_reward, force_scalar, bad),
+                 Win{head, n_step, gamma}, (float*)outs[6], (int32_t*)outs[7]};
+  const Buf& b = p.s.buf;
   for (long long blk = 0; blk < rbuf::sample_blocks(n); blk++) {
-    Tr first[BLOCK / 64][W_SAMPLES];
-    long long last[BLOCK / 64][W_SAMPLES];
+    sample_walk::WaveIds ids[BLOCK / 64];
     for (int wave = 0; wave < BLOCK / 64; wave++) {
       const long long j0 = rbuf::wave_first(blk, wave);
       const int nw = rbuf::wave_count(n, blk, wave);
@@ -59,10 +42,10 @@ extern "C" int ns_host_sample(void** bufs, long long T, long long B, int obs_dim
         const int half = lane / HALF, i = lane % HALF;
         raw[lane] = 0; mine[lane] = Tr{0, false};
         if (half < nw) {
-          raw[lane] = raw_id(index, seed, draw, j0 + half, N);
+          raw[lane] = raw_id(index, seed, draw, j0 + half, p.s.N);
           mine[lane] = guard_id(raw[lane], T, B);
         }
-        st[lane] = lane_step(b, mine[lane], w, i);
+        st[lane] = lane_step(b, mine[lane], p.win, i);
         if (st[lane].end) ends |= 1ull << lane;
       }
       const int m_half[W_SAMPLES] = {window_len((uint32_t)ends), window_len((uint32_t)(ends >> HALF))};
@@ -77,29 +60,13 @@ extern "C" int ns_host_sample(void** bufs, long long T, long long B, int obs_dim
         const int last_flags = st[mate + (m ? m - 1 : 0)].flags;
         const long long end_id = mine[lane].ok ? step_slot(T, B, mine[lane].s, m - 1).s : 0;
         if (half < nw && i == 0) {
-          lane_flat(o, nm, j0 + half, raw[lane], mine[lane], m, acc, g, last_flags);
+          lane_flat(Out{p.s.out, p.discount, p.steps}, p.s.norm, j0 + half, raw[lane], mine[lane], m, acc, g, last_flags);
           if (!mine[lane].ok) *bad += 1;
         }
-        if (i == 0) { first[wave][half] = mine[lane]; last[wave][half] = end_id; }   // what __shfl(.., half * HALF, 64) hands every lane
-      }
-      if (o.base.action)
-        for (int lane = 0; lane < 64; lane++)
-          for (int k = 0; k < nw; k++) rbuf::lane_action(b, o.base, j0 + k, first[wave][k], lane, vec_act);
-    }
-    if (!o.base.obs && !o.base.next_obs) continue;
-    for (int c0 = 0; c0 < obs_dim; c0 += PASS_COLS) {
-      if (norm)
-        for (int t = 0; t < BLOCK; t++) rbuf::thread_pass_stats(nm, obs_dim, c0, t, s_mean, s_inv);
-      for (int wave = 0; wave < BLOCK / 64; wave++) {
-        const long long j0 = rbuf::wave_first(blk, wave);
-        const int nw = rbuf::wave_count(n, blk, wave);
-        for (int lane = 0; lane < 64; lane++) {
-          double mean[LANE_COLS] = {0, 0, 0, 0}, inv[LANE_COLS] = {0, 0, 0, 0};
-          if (norm) rbuf::lane_pass_stats(s_mean, s_inv, obs_dim, c0, lane, vec_obs, mean, inv);
-          for (int k = 0; k < nw; k++) lane_obs_pass(b, o, nm, j0 + k, first[wave][k], last[wave][k], c0, lane, vec_obs, mean, inv);
-        }
+        if (i == 0) { ids[wave].first[half] = mine[lane]; ids[wave].last[half] = end_id; }   // what __shfl(.., half * HALF, 64) hands every lane
       }
     }
+    sample_walk::block_rows(p.s, blk, ids);
   }
   return 0;
 }

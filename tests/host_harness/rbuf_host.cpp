@@ -5,18 +5,10 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../random-envs_amd/csrc/replay_buffer.hpp"
+#include "sample_walk.hpp"
 
 using namespace rbuf;
-
-namespace {
-
-// bufs: obs, next_obs, action, reward, done, timeout
-Buf make_buf(void** p, long long T, long long B, int obs_dim, int act_dim) {
-  return Buf{(uint32_t*)p[0], (uint32_t*)p[1], (uint32_t*)p[2], (float*)p[3], (uint8_t*)p[4], (uint8_t*)p[5], T, B, obs_dim, act_dim};
-}
-
-}  // namespace
+using sample_walk::make_buf;
 
 extern "C" void rb_host_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out) { philox4x32_10(ctr, key, out); }
 
@@ -47,55 +39,33 @@ extern "C" int rb_host_add(void** bufs, long long T, long long B, int obs_dim, i
   return 0;
 }
 
-// outs: obs [n][obs_dim], next_obs [n][obs_dim], action [n][act_dim], reward, done [n] f32, index [n] int64 (each may be null).
-// index == null: the ids are drawn over size * B transitions.  stats == null: no normalisation.  force_scalar != 0: the 4-byte path even
-// where 16-byte accesses are allowed (both must give the same bits).
+// The sample launch; the arguments are those of sample_walk::make_params.  Returns -1 for the arguments the C-ABI refuses.
 extern "C" int rb_host_sample(void** bufs, long long T, long long B, int obs_dim, int act_dim, const long long* index, long long n, long long size,
                               unsigned long long seed, unsigned long long draw, void** outs, const double* stats, int norm_obs, int norm_reward,
                               double eps, double clip_obs, double clip_reward, int force_scalar, long long* bad) {
-  const Buf b = make_buf(bufs, T, B, obs_dim, act_dim);
   if (!index && (size < 1 || size > T)) return -1;
   if (n < 0) return -1;
-  const Out o{(uint32_t*)outs[0], (uint32_t*)outs[1], (uint32_t*)outs[2], (float*)outs[3], (float*)outs[4], (long long*)outs[5]};
-  const Norm nm{stats, obs_dim + 1, norm_obs, norm_reward, eps, clip_obs, clip_reward};
-  const long long N = index ? T * B : size * B;
-  const bool vec_obs = !force_scalar && obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, o.obs, o.next_obs);
-  const bool vec_act = !force_scalar && act_dim % 4 == 0 && postpass::all_aligned16(b.action, o.action);
-  const bool norm = nm.stats && nm.norm_obs;
-  double s_mean[PASS_COLS], s_inv[PASS_COLS];
+  const SampleParams p = sample_walk::make_params(bufs, T, B, obs_dim, act_dim, index, n, size, seed, draw, outs, stats, norm_obs, norm_reward, eps,
+                                                  clip_obs, clip_reward, force_scalar, bad);
   for (long long blk = 0; blk < sample_blocks(n); blk++) {
-    Tr mine[BLOCK / 64][64];
+    sample_walk::WaveIds ids[BLOCK / 64];
     for (int wave = 0; wave < BLOCK / 64; wave++) {
       const long long j0 = wave_first(blk, wave);
       const int nw = wave_count(n, blk, wave);
+      Tr mine[64];                                     // lane k holds the id of the wave's k-th sample
       for (int lane = 0; lane < 64; lane++) {
-        mine[wave][lane] = Tr{0, false};
+        mine[lane] = Tr{0, false};
         if (lane < nw) {
           const long long j = j0 + lane;
-          const long long raw = index ? index[j] : sample_id(seed, draw, (uint64_t)j, N);
-          mine[wave][lane] = guard_id(raw, T, B);
-          lane_flat(b, o, nm, j, raw, mine[wave][lane]);
-          if (!mine[wave][lane].ok) *bad += 1;
+          const long long raw = raw_id(index, seed, draw, j, p.N);
+          mine[lane] = guard_id(raw, T, B);
+          lane_flat(p.buf, p.out, p.norm, j, raw, mine[lane]);
+          if (!mine[lane].ok) *bad += 1;
         }
       }
-      if (o.action)
-        for (int lane = 0; lane < 64; lane++)
-          for (int k = 0; k < nw; k++) lane_action(b, o, j0 + k, mine[wave][k], lane, vec_act);
+      for (int k = 0; k < W_SAMPLES; k++) { ids[wave].first[k] = mine[k]; ids[wave].last[k] = mine[k].s; }   // the __shfl reads of lane k
     }
-    if (!o.obs && !o.next_obs) continue;
-    for (int c0 = 0; c0 < obs_dim; c0 += PASS_COLS) {
-      if (norm)
-        for (int t = 0; t < BLOCK; t++) thread_pass_stats(nm, obs_dim, c0, t, s_mean, s_inv);
-      for (int wave = 0; wave < BLOCK / 64; wave++) {
-        const long long j0 = wave_first(blk, wave);
-        const int nw = wave_count(n, blk, wave);
-        for (int lane = 0; lane < 64; lane++) {
-          double mean[LANE_COLS] = {0, 0, 0, 0}, inv[LANE_COLS] = {0, 0, 0, 0};
-          if (norm) lane_pass_stats(s_mean, s_inv, obs_dim, c0, lane, vec_obs, mean, inv);
-          for (int k = 0; k < nw; k++) lane_obs_pass(b, o, nm, j0 + k, mine[wave][k], c0, lane, vec_obs, mean, inv);
-        }
-      }
-    }
+    sample_walk::block_rows(p, blk, ids);
   }
   return 0;
 }

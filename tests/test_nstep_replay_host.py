@@ -239,6 +239,33 @@ def test_normalised_outputs_within_one_ulp(T, B, D, A, norm_obs, norm_reward):
             assert_outputs({k: results[0][k] for k in PLAIN}, plain, "n_step == 1 against the plain normalised gather")
 
 
+# ------------------------------------------------------------------------------------------------- one tail for both launches
+@pytest.mark.parametrize("T,B,D,A", [(3, 63, 11, 3), (2, 5, 376, 17)])
+def test_one_step_window_equals_the_plain_launch_byte_for_byte(T, B, D, A):
+    """Both launches end in the same rows function (rbuf::block_rows; sample_walk.hpp here): with n_step = 1 the window is its first id, so
+    rb_host_sample and ns_host_sample on the same buffers must agree on every byte of every shared output and on ``bad`` -- drawn and
+    gathered, raw and normalised, 16-byte and 4-byte paths.  Both sides go through the same walk, so this pins that the two HEADS agree; a fault
+    in the shared walk itself is what the numpy-oracle tests above and in test_replay_buffer_host.py catch."""
+    rng = np.random.default_rng(T + B + D)
+    bufs = window_buffers(rng, T, B, D, A, 0.15)
+    norm = random_norm(rng, D)
+    n = 37                                           # sample blocks of 8: the last one ends early
+    idx = rng.integers(0, T * B, size=n).astype(np.int64)
+    idx[[3, 20, 36]] = (-1, T * B, 2 ** 62)          # out of range: zeros on both sides, counted on both sides
+    for index in (None, idx):
+        for nm in (None, norm):
+            for scalar in (False, True):
+                kw = dict(index=index, size=None if index is not None else T, seed=5, draw=2, norm=nm, force_scalar=scalar)
+                rc_p, plain, bad_p = rb_host.sample(bufs, n, **kw)
+                rc_n, got, bad_n = host.sample(bufs, n, T - 1, 1, 0.97, **kw)
+                what = "drawn=%d norm=%d scalar=%d" % (index is None, nm is not None, scalar)
+                assert rc_p == 0 and rc_n == 0, what
+                assert bad_p == bad_n == (0 if index is None else 3), what
+                assert set(plain) == set(got) - {"discount", "steps"} and set(plain) >= set(PLAIN), what
+                for k in plain:
+                    assert plain[k].dtype == got[k].dtype and plain[k].tobytes() == got[k].tobytes(), "%s: %s" % (what, k)
+
+
 # ------------------------------------------------------------------------------------------------- sanitizers, surface
 def test_host_functions_stay_inside_exactly_sized_buffers_under_sanitizers(tmp_path):
     """tests/host_harness/nstep_sanitize_main.cpp: a program of its own (the sanitizer runtimes are linked into it; nothing is preloaded)"""
