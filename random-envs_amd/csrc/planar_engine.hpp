@@ -86,10 +86,11 @@ REX_HD void kinematics(const T (&q)[S::NV], const PlanarGeom<T, S>& G, Kin<T, S>
 // Joint-space inertia (lower triangle, only coupled entries are touched) and bias forces.
 // M: composite-body recursion about each joint anchor; bias: planar Newton-Euler with the
 // velocity-product accelerations (no angular term in 2-D) and gravity.
-template <class T, class S>
+// TM = hess_t<T, S>: the type M is formed and kept in (planar_spec.hpp); the bias forces stay in T.
+template <class T, class S, class TM>
 REX_HD void mass_and_bias(const T (&v)[S::NV], const PlanarGeom<T, S>& G, const LaneParams<T, S>& P,
-                          const Kin<T, S>& K, T (&M)[S::NV][S::NV], T (&bias)[S::NV]) {
-  T mu[S::NB], h[S::NB][2], I[S::NB];   // composite mass, first moment about anchor, inertia about anchor
+                          const Kin<T, S>& K, TM (&M)[S::NV][S::NV], T (&bias)[S::NV]) {
+  TM mu[S::NB], h[S::NB][2], I[S::NB];   // composite mass, first moment about anchor, inertia about anchor
   T w[S::NB], Aacc[S::NB][2], Phi[S::NB][2], N[S::NB];
   static_for<0, S::NB>([&](auto II) {
     constexpr int i = II;
@@ -102,8 +103,8 @@ REX_HD void mass_and_bias(const T (&v)[S::NV], const PlanarGeom<T, S>& G, const 
       Aacc[i][1] = Aacc[p][1] - w2 * (K.A[i][1] - K.A[p][1]);
     }
     T m = P.mass[i];
-    mu[i] = m; h[i][0] = m * K.rc[i][0]; h[i][1] = m * K.rc[i][1];
-    I[i] = G.iyy[i] + m * (K.rc[i][0] * K.rc[i][0] + K.rc[i][1] * K.rc[i][1]);
+    mu[i] = TM(m); h[i][0] = TM(m) * TM(K.rc[i][0]); h[i][1] = TM(m) * TM(K.rc[i][1]);
+    I[i] = TM(G.iyy[i]) + TM(m) * (TM(K.rc[i][0]) * TM(K.rc[i][0]) + TM(K.rc[i][1]) * TM(K.rc[i][1]));
     T wi2 = w[i] * w[i];
     T ax = Aacc[i][0] - wi2 * K.rc[i][0], az = Aacc[i][1] - wi2 * K.rc[i][1] + T(S::GRAVITY);
     Phi[i][0] = m * ax; Phi[i][1] = m * az;
@@ -112,43 +113,43 @@ REX_HD void mass_and_bias(const T (&v)[S::NV], const PlanarGeom<T, S>& G, const 
   static_rfor<1, S::NB>([&](auto CC) {   // children into parents
     constexpr int c = CC; constexpr int p = S::parent[c];
     T dx = K.A[c][0] - K.A[p][0], dz = K.A[c][1] - K.A[p][1];
-    I[p] += I[c] + T(2) * (dx * h[c][0] + dz * h[c][1]) + mu[c] * (dx * dx + dz * dz);
-    h[p][0] += h[c][0] + mu[c] * dx; h[p][1] += h[c][1] + mu[c] * dz;
+    I[p] += I[c] + TM(2) * (TM(dx) * h[c][0] + TM(dz) * h[c][1]) + mu[c] * (TM(dx) * TM(dx) + TM(dz) * TM(dz));
+    h[p][0] += h[c][0] + mu[c] * TM(dx); h[p][1] += h[c][1] + mu[c] * TM(dz);
     mu[p] += mu[c];
     N[p] += N[c] + dz * Phi[c][0] - dx * Phi[c][1];
     Phi[p][0] += Phi[c][0]; Phi[p][1] += Phi[c][1];
   });
-  M[0][0] = mu[0]; M[1][1] = mu[0]; M[1][0] = T(0);
+  M[0][0] = mu[0]; M[1][1] = mu[0]; M[1][0] = TM(0);
   bias[0] = Phi[0][0]; bias[1] = Phi[0][1];
   static_for<0, S::NB>([&](auto JJ) {
     constexpr int j = JJ;
     constexpr T sj = T(S::sgn[j]);
-    M[j + 2][0] = sj * h[j][1];
-    M[j + 2][1] = -sj * h[j][0];
-    M[j + 2][j + 2] = I[j] + G.armature[j];
+    M[j + 2][0] = TM(sj) * h[j][1];
+    M[j + 2][1] = -TM(sj) * h[j][0];
+    M[j + 2][j + 2] = I[j] + TM(G.armature[j]);
     bias[j + 2] = sj * N[j];
     static_for<0, j>([&](auto II) {
       constexpr int i = II;
       if constexpr (is_anc_or_self<S>(i, j)) {
         constexpr T si = T(S::sgn[i]);
-        M[j + 2][i + 2] = si * sj * (I[j] + (K.A[j][0] - K.A[i][0]) * h[j][0] + (K.A[j][1] - K.A[i][1]) * h[j][1]);
+        M[j + 2][i + 2] = TM(si * sj) * (I[j] + TM(K.A[j][0] - K.A[i][0]) * h[j][0] + TM(K.A[j][1] - K.A[i][1]) * h[j][1]);
       }
     });
   });
 }
 
-// y = M x using the lower triangle + tree sparsity
-template <class T, class S>
-REX_HD void sym_matvec(const T (&M)[S::NV][S::NV], const T (&x)[S::NV], T (&y)[S::NV]) {
+// y = M x using the lower triangle + tree sparsity (summed in M's type)
+template <class T, class S, class TM, class TY>
+REX_HD void sym_matvec(const TM (&M)[S::NV][S::NV], const T (&x)[S::NV], TY (&y)[S::NV]) {
   static_for<0, S::NV>([&](auto II) {
     constexpr int i = II;
-    T acc = M[i][i] * x[i];
+    TM acc = M[i][i] * TM(x[i]);
     static_for<0, S::NV>([&](auto JJ) {
       constexpr int j = JJ;
-      if constexpr (j < i) { if constexpr (dof_coupled<S>(i, j)) acc += M[i][j] * x[j]; }
-      else if constexpr (j > i) { if constexpr (dof_coupled<S>(i, j)) acc += M[j][i] * x[j]; }
+      if constexpr (j < i) { if constexpr (dof_coupled<S>(i, j)) acc += M[i][j] * TM(x[j]); }
+      else if constexpr (j > i) { if constexpr (dof_coupled<S>(i, j)) acc += M[j][i] * TM(x[j]); }
     });
-    y[i] = acc;
+    y[i] = TY(acc);
   });
 }
 
@@ -264,15 +265,17 @@ REX_HD void jt_accum(const Kin<T, S>& K, T px, T pz, T ft, T fn, T (&g)[S::NV]) 
   });
 }
 // H += sum_ab u_a^T C u_b over the dofs of body B's root path, u_a = (Jt_a, Jn_a), C = [[ctt,cnt],[cnt,cnn]]
-template <class T, class S, int B>
-REX_HD void hess_accum(const Kin<T, S>& K, T px, T pz, T ctt, T cnt, T cnn, T (&H)[S::NV][S::NV]) {
-  T ut[S::NV], un[S::NV], wt[S::NV], wn[S::NV];
-  ut[0] = T(1); un[0] = T(0); ut[1] = T(0); un[1] = T(1);
+// (TH = hess_t<T, S>: the columns are formed in T as everywhere else, their products are formed and summed in TH)
+template <class T, class S, int B, class TH>
+REX_HD void hess_accum(const Kin<T, S>& K, T px, T pz, T ctt_, T cnt_, T cnn_, TH (&H)[S::NV][S::NV]) {
+  TH ut[S::NV], un[S::NV], wt[S::NV], wn[S::NV];
+  const TH ctt = TH(ctt_), cnt = TH(cnt_), cnn = TH(cnn_);
+  ut[0] = TH(1); un[0] = TH(0); ut[1] = TH(0); un[1] = TH(1);
   static_for<0, S::NB>([&](auto JJ) {
     constexpr int j = JJ;
     if constexpr (is_anc_or_self<S>(j, B)) {
       constexpr T sj = T(S::sgn[j]);
-      ut[j + 2] = sj * (pz - K.A[j][1]); un[j + 2] = -sj * (px - K.A[j][0]);
+      ut[j + 2] = TH(sj * (pz - K.A[j][1])); un[j + 2] = TH(-sj * (px - K.A[j][0]));
     }
   });
   static_for<0, S::NV>([&](auto AA) {
@@ -309,11 +312,12 @@ REX_HD void jt_accum_pre(const T (&jt)[S::NB], const T (&jn)[S::NB], T ft, T fn,
   g[0] += ft; g[1] += fn;
   static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr (is_anc_or_self<S>(j, B)) g[j + 2] += jt[j] * ft + jn[j] * fn; });
 }
-template <class T, class S, int B>
-REX_HD void hess_accum_pre(const T (&jt)[S::NB], const T (&jn)[S::NB], T ctt, T cnt, T cnn, T (&H)[S::NV][S::NV]) {
-  T ut[S::NV], un[S::NV], wt[S::NV], wn[S::NV];
-  ut[0] = T(1); un[0] = T(0); ut[1] = T(0); un[1] = T(1);
-  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr (is_anc_or_self<S>(j, B)) { ut[j + 2] = jt[j]; un[j + 2] = jn[j]; } });
+template <class T, class S, int B, class TH>
+REX_HD void hess_accum_pre(const T (&jt)[S::NB], const T (&jn)[S::NB], T ctt_, T cnt_, T cnn_, TH (&H)[S::NV][S::NV]) {
+  TH ut[S::NV], un[S::NV], wt[S::NV], wn[S::NV];
+  const TH ctt = TH(ctt_), cnt = TH(cnt_), cnn = TH(cnn_);
+  ut[0] = TH(1); un[0] = TH(0); ut[1] = TH(0); un[1] = TH(1);
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr (is_anc_or_self<S>(j, B)) { ut[j + 2] = TH(jt[j]); un[j + 2] = TH(jn[j]); } });
   static_for<0, S::NV>([&](auto AA) {
     constexpr int a = AA;
     if constexpr (a < 2 || is_anc_or_self<S>(a - 2, B)) { wt[a] = ctt * ut[a] + cnt * un[a]; wn[a] = cnt * ut[a] + cnn * un[a]; }
@@ -326,6 +330,23 @@ REX_HD void hess_accum_pre(const T (&jt)[S::NB], const T (&jn)[S::NB], T ctt, T 
         if constexpr (b < 2 || is_anc_or_self<S>(b - 2, B)) H[a][b] += wt[a] * ut[b] + wn[a] * un[b];
       });
   });
+}
+
+// The wide gradient (hess_t<T, S> != T): one floor slot's term J^T D min(0, J qacc - aref) re-evaluated in TH from the slot's hinge columns
+// (bodies of MASK; zero for non-ancestors), with the edges the T pass found active.  A row's residual is the small difference of J qacc and
+// aref, and D times its fp32 rounding is a force of the size of the forces M has to balance: the Newton step from a point far from the
+// minimiser (a cold start, a contact made in this stage) then lands beside it however exact its Hessian is.
+template <class S> constexpr unsigned anc_mask(int b) { unsigned m = 0; for (int j = 0; j < S::NB; j++) if (is_anc_or_self<S>(j, b)) m |= 1u << j; return m; }
+template <class T, class S, unsigned MASK, class TH>
+REX_HD void slot_grad_wide(const T (&jt)[S::NB], const T (&jn)[S::NB], const T (&qacc)[S::NV], T mu_, T an_, T at_, T D_, bool s1, bool s2, bool s3, TH (&gh)[S::NV]) {
+  TH t = TH(qacc[0]), n = TH(qacc[1]);
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr ((MASK >> j) & 1u) { t += TH(jt[j]) * TH(qacc[j + 2]); n += TH(jn[j]) * TH(qacc[j + 2]); } });
+  const TH mu = TH(mu_), an = TH(an_), at = TH(at_), D = TH(D_);
+  const TH r1 = n + mu * t - (an + at), r2 = n - mu * t - (an - at), r3 = n - an;
+  const TH f1 = s1 ? -D * r1 : TH(0), f2 = s2 ? -D * r2 : TH(0), f3 = s3 ? -D * r3 : TH(0);
+  const TH ft = -(mu * (f1 - f2)), fn = -(f1 + f2 + TH(2) * f3);
+  gh[0] += ft; gh[1] += fn;
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr ((MASK >> j) & 1u) gh[j + 2] += TH(jt[j]) * ft + TH(jn[j]) * fn; });
 }
 
 // capsule centre / half-axis of geom g in world axes (relative to the root anchor)
@@ -681,6 +702,16 @@ REX_HD bool corr_step(const T (&H)[S::NV][S::NV], bool two, bool use, unsigned p
   return good;
 }
 
+// "The gradient is at rounding level": |g|^2 <= tol2 (|M a|^2 + |f|^2) over all dofs together -- and, where the model's inertias span the
+// search box of masses AND lengths (WIDE_HESSIAN), dof by dof: a 0.5 kg, 15 cm foot on a tumbling 50 kg walker balances forces 1e-5 of the
+// whole tree's, so a gradient that is nothing beside |f| still moves the foot's own acceleration by half a per cent.  NaN counts as small.
+template <class T, class S>
+REX_HD bool grad_at_rounding_level(const T (&g)[S::NV], const T (&Ma)[S::NV], const T (&f)[S::NV], T gn, T fref, T tol2) {
+  bool small = !(gn > tol2 * fref);
+  if constexpr (S::WIDE_HESSIAN) static_for<0, S::NV>([&](auto II) { constexpr int i = II; small = small && !(g[i] * g[i] > tol2 * (Ma[i] * Ma[i] + f[i] * f[i])); });
+  return small;
+}
+
 // Primal Newton solve of   min_a 0.5 (a-a0)^T M (a-a0) + sum_rows 0.5 D min(0, J a - aref)^2
 // ([3P] engine_solver, Newton, pyramidal cones): exact Hessian M + J^T D_active J with the tree
 // sparsity of M, L^T D L factorisation, exact line search on the piecewise-quadratic 1-D cost.
@@ -696,7 +727,7 @@ template <bool BR> REX_HD bool any_lane(bool x) { if constexpr (BR) return REX_W
 // LAZY: the line-search sums (M sr, phi'(0), the Gauss curvature, phi' / phi'' at alpha = 1) and the carry of Ma are computed only on the
 // paths that read them -- see "line search" and "carry" in the iteration below.  Same operations on the same values, so the same bits.
 template <class T, class S, bool SELF, unsigned SLOTS, bool BR, bool PAIR = false, bool LAZY = false, int MAXIT = 24>
-REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
+REX_HD SolveStats solve_newton(const hess_t<T, S> (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
                                const Kin<T, S>& K, const Constraints<T, S>& C, const SelfRows<T, S>& R,
                                const LaneParams<T, S>& P, T (&qacc)[S::NV], bool warm, bool have_a0, int ls_max, int ls_free = 0, int corr = 1) {
   // MuJoCo starts at qacc_smooth (warmstart is disabled in all the XMLs); the minimiser is unique, so
@@ -751,6 +782,14 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     unsigned lim_on = 0, e1 = 0, e2 = 0, e3 = 0, self_on = 0;
     T gs[PAIR ? S::NV : 1];   // PAIR: this lane's slot contributions to the gradient
     if constexpr (PAIR) static_for<0, S::NV>([&](auto II) { gs[II] = T(0); });
+    // WIDE: the right-hand side of the Newton system is the gradient evaluated in TH at the same point with the same active rows (slot_grad_wide);
+    // g itself, in T, goes on deciding the sets, the exits and the line search
+    using TH = hess_t<T, S>;   // (planar_spec.hpp: fp64 for the fp32 walker2d, T otherwise)
+    constexpr bool WIDE = !std::is_same_v<TH, T>;
+    static_assert(!(WIDE && SELF && S::NSELF > 0), "wide gradient: no capsule-capsule rows");
+    TH gh[WIDE ? S::NV : 1], ghs[(WIDE && PAIR) ? S::NV : 1];
+    if constexpr (WIDE) { sym_matvec<T, S>(M, qacc, gh); static_for<0, S::NV>([&](auto II) { gh[II] -= TH(qfrc_smooth[II]); }); }
+    if constexpr (WIDE && PAIR) static_for<0, S::NV>([&](auto II) { ghs[II] = TH(0); });
     static_for<1, S::NB>([&](auto JJ) {
       constexpr int j = JJ;
       if constexpr (S::limited[j]) {
@@ -758,6 +797,7 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
         bool on = ((C.lim_mask >> j) & 1u) && jar < T(0);
         if (on) lim_on |= 1u << j;
         g[j + 2] += on ? C.lsig[j] * C.lD[j] * jar : T(0);
+        if constexpr (WIDE) gh[j + 2] += on ? TH(C.lsig[j]) * TH(C.lD[j]) * (TH(C.lsig[j]) * TH(qacc[j + 2]) - TH(C.laref[j])) : TH(0);
       }
     });
     for_slots<SLOTS>([&](auto KK) {
@@ -776,10 +816,17 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
           if constexpr (BR) jt_accum<T, S, b>(K, cpx[k], cpz[k], -(mu * (f1 - f2)), -(f1 + f2 + T(2) * f3), g);
           else if constexpr (PAIR) jt_accum_pre<T, S, b>(Jt[k], Jn[k], -(mu * (f1 - f2)), -(f1 + f2 + T(2) * f3), gs);
           else jt_accum_pre<T, S, b>(Jt[k], Jn[k], -(mu * (f1 - f2)), -(f1 + f2 + T(2) * f3), g);
+          if constexpr (WIDE) {
+            if constexpr (BR) { T cjt[S::NB], cjn[S::NB]; point_jac<T, S, b>(K, cpx[k], cpz[k], cjt, cjn);
+                                slot_grad_wide<T, S, anc_mask<S>(b)>(cjt, cjn, qacc, mu, C.an[k], C.at[k], C.D[k], s1, s2, s3, gh); }
+            else if constexpr (PAIR) slot_grad_wide<T, S, anc_mask<S>(b)>(Jt[k], Jn[k], qacc, mu, C.an[k], C.at[k], C.D[k], s1, s2, s3, ghs);
+            else slot_grad_wide<T, S, anc_mask<S>(b)>(Jt[k], Jn[k], qacc, mu, C.an[k], C.at[k], C.D[k], s1, s2, s3, gh);
+          }
         }
       }
     });
     if constexpr (PAIR) {   // both ends' contributions and active edges, identical in both lanes (commutative sums)
+      if constexpr (WIDE) static_for<0, S::NV>([&](auto II) { constexpr int i = II; gh[i] += ghs[i] + pair_xchg(ghs[i]); });
       static_for<0, S::NV>([&](auto II) { constexpr int i = II; g[i] += gs[i] + pair_xchg(gs[i]); });
       e1 |= pair_xchg(e1); e2 |= pair_xchg(e2); e3 |= pair_xchg(e3);
     }
@@ -802,21 +849,21 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     static_for<0, S::NV>([&](auto II) { gn += g[II] * g[II]; });
     const bool same_set = lim_on == p_lim && e1 == p_e1 && e2 == p_e2 && e3 == p_e3 && self_on == p_self;
     p_lim = lim_on; p_e1 = e1; p_e2 = e2; p_e3 = e3; p_self = self_on;
-    lane_done = lane_done || same_set || !(gn > tol2 * fref);   // NaN counts as done
+    lane_done = lane_done || same_set || grad_at_rounding_level<T, S>(g, Ma, qfrc_smooth, gn, fref, tol2);   // NaN counts as done
     if (!REX_WAVE_ANY(!lane_done)) break;
     REX_PSTAMP(s_1, gn);
     REX_PACC(5, s_0, s_1);
     REX_COUNT(pass2, 1);
     REX_MARK("pass2_hess");
     // ---- pass 2: Hessian of the current active set, Newton direction ------------------------
-    T H[S::NV][S::NV];
+    TH H[S::NV][S::NV];
     static_for<0, S::NV>([&](auto II) { constexpr int i = II;
-      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) H[i][j] = M[i][j]; }); });
+      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) H[i][j] = TH(M[i][j]); }); });
     static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ;
-      if constexpr (S::limited[j]) H[j + 2][j + 2] += ((lim_on >> j) & 1u) ? C.lD[j] : T(0); });
-    T Hs[PAIR ? S::NV : 1][PAIR ? S::NV : 1];   // PAIR: this lane's slot contributions to the Hessian
+      if constexpr (S::limited[j]) H[j + 2][j + 2] += TH(((lim_on >> j) & 1u) ? C.lD[j] : T(0)); });
+    TH Hs[PAIR ? S::NV : 1][PAIR ? S::NV : 1];   // PAIR: this lane's slot contributions to the Hessian
     if constexpr (PAIR) static_for<0, S::NV>([&](auto II) { constexpr int i = II;
-      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hs[i][j] = T(0); }); });
+      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hs[i][j] = TH(0); }); });
     for_slots<SLOTS>([&](auto KK) {
       {
         constexpr int k = KK; constexpr int gg = k / 2; constexpr int b = S::geom_body[gg];
@@ -842,17 +889,21 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
           jt_accum<T, S, bb>(K, R.px[p], R.pz[p], R.nx[p], R.nz[p], row); jt_accum<T, S, ba>(K, R.px[p], R.pz[p], -R.nx[p], -R.nz[p], row);
           T d = ((self_on >> p) & 1u) ? R.D[p] : T(0);
           static_for<0, S::NV>([&](auto AA) { constexpr int a = AA;
-            static_for<0, a + 1>([&](auto BB) { constexpr int bq = BB; if constexpr (dof_coupled<S>(a, bq)) H[a][bq] += d * row[a] * row[bq]; }); });
+            static_for<0, a + 1>([&](auto BB) { constexpr int bq = BB; if constexpr (dof_coupled<S>(a, bq)) H[a][bq] += TH(d) * TH(row[a]) * TH(row[bq]); }); });
         }
       });
     }
-    REX_PSTAMP(s_h, H[S::NV - 1][0] + H[S::NV - 1][S::NV - 1] + H[2][2]);
+    REX_PSTAMP(s_h, T(H[S::NV - 1][0] + H[S::NV - 1][S::NV - 1] + H[2][2]));
     REX_PACC(7, s_1, s_h);
     REX_MARK("pass2_ldl");
-    ldl_factor<T, S>(H);
+    ldl_factor<TH, S>(H);
     T sr[S::NV];
-    static_for<0, S::NV>([&](auto II) { sr[II] = -g[II]; });
-    ldl_solve<T, S>(H, sr);
+    {
+      TH sh[S::NV];
+      static_for<0, S::NV>([&](auto II) { if constexpr (WIDE) sh[II] = -gh[II]; else sh[II] = TH(-g[II]); });
+      ldl_solve<TH, S>(H, sh);
+      static_for<0, S::NV>([&](auto II) { sr[II] = T(sh[II]); });
+    }
     REX_PSTAMP(s_l, sr[0] + sr[S::NV - 1]);
     REX_PACC(8, s_h, s_l);
     REX_MARK("pass2_ls");
@@ -981,7 +1032,9 @@ REX_HD SolveStats solve_newton(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth
     // 32-env wave a full iteration is paid by everybody whenever ONE env needs it.  x2 is accepted as converged only if the
     // set at x2 equals the set at x1 (then it is that set's exact minimiser); otherwise the regular iterations go on from x2.
     // PAIR: the lane that owns the toggled slot computes the step, the other one contributes zero; limits: the even lane.
-    if constexpr (!BR && !SELF) {
+    // (not WIDE: the correction's right-hand side is built from T residuals at x1, which is the rounding the wide gradient exists to avoid --
+    // walker2d corners with it: max |dqvel|rel 2.0e-4 against 2.3e-5 without; a toggled group there costs a regular iteration)
+    if constexpr (!BR && !SELF && !WIDE) {
       REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
       // groups are dealt to the two lanes of a pair; host builds deal them to two virtual lanes of the one lane (same arithmetic, so the CPU
       // tests cover it); the one-lane device kernels keep the single-group form (a second group there is two more solves and their registers)
@@ -1114,7 +1167,7 @@ REX_HD void build_rows(const Kin<T, S>& K, const Constraints<T, S>& C, const Sel
   L.n = n;
 }
 template <class T, class S, int MAXIT = 24>
-REX_HD SolveStats solve_newton_rolled(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV], const RowList<T, S>& L,
+REX_HD SolveStats solve_newton_rolled(const hess_t<T, S> (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV], const RowList<T, S>& L,
                                       T (&qacc)[S::NV], bool warm, bool have_a0, int ls_max, int ls_free) {
   const int n = L.n;
   const bool has_rows = n > 0;
@@ -1145,26 +1198,31 @@ REX_HD SolveStats solve_newton_rolled(const T (&M)[S::NV][S::NV], const T (&qfrc
     static_for<0, S::NV>([&](auto II) { gn += g[II] * g[II]; });
     const bool same_set = on == p_on;
     p_on = on;
-    lane_done = lane_done || same_set || !(gn > tol2 * fref);
+    lane_done = lane_done || same_set || grad_at_rounding_level<T, S>(g, Ma, qfrc_smooth, gn, fref, tol2);
     if (!REX_WAVE_ANY(!lane_done)) break;
-    T H[S::NV][S::NV];
+    using TH = hess_t<T, S>;
+    TH H[S::NV][S::NV];
     static_for<0, S::NV>([&](auto II) { constexpr int i = II;
-      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) H[i][j] = M[i][j]; }); });
+      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) H[i][j] = TH(M[i][j]); }); });
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
 #endif
     for (int r = 0; r < n; r++) {
       if ((on >> r) & 1ull) {
-        T row[S::NV]; static_for<0, S::NV>([&](auto II) { row[II] = L.J[r][II]; });
-        const T d = L.D[r];
+        TH row[S::NV]; static_for<0, S::NV>([&](auto II) { row[II] = TH(L.J[r][II]); });
+        const TH d = TH(L.D[r]);
         static_for<0, S::NV>([&](auto AA) { constexpr int a = AA;
           static_for<0, a + 1>([&](auto BB) { constexpr int b = BB; if constexpr (dof_coupled<S>(a, b)) H[a][b] += d * row[a] * row[b]; }); });
       }
     }
-    ldl_factor<T, S>(H);
+    ldl_factor<TH, S>(H);
     T sr[S::NV];
-    static_for<0, S::NV>([&](auto II) { sr[II] = -g[II]; });
-    ldl_solve<T, S>(H, sr);
+    {
+      TH sh[S::NV];
+      static_for<0, S::NV>([&](auto II) { sh[II] = TH(-g[II]); });
+      ldl_solve<TH, S>(H, sh);
+      static_for<0, S::NV>([&](auto II) { sr[II] = T(sh[II]); });
+    }
     T Ms[S::NV];
     sym_matvec<T, S>(M, sr, Ms);
     T q1 = T(0), q2 = T(0), d0 = T(0);
@@ -1289,10 +1347,11 @@ REX_HD void list_accum(const T (&jt)[S::NB], const T (&jn)[S::NB], T ft, T fn, T
   g[0] += ft; g[1] += fn;
   static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr ((SUB >> j) & 1u) g[j + 2] += jt[j] * ft + jn[j] * fn; });
 }
-template <class T, class S, unsigned SUB>
-REX_HD void list_hess(const T (&jt)[S::NB], const T (&jn)[S::NB], T ctt, T cnt, T cnn, T (&H)[S::NV][S::NV]) {
-  T wt[S::NB], wn[S::NB];
-  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr ((SUB >> j) & 1u) { wt[j] = ctt * jt[j] + cnt * jn[j]; wn[j] = cnt * jt[j] + cnn * jn[j]; } });
+template <class T, class S, unsigned SUB, class TH>
+REX_HD void list_hess(const T (&jt_)[S::NB], const T (&jn_)[S::NB], T ctt_, T cnt_, T cnn_, TH (&H)[S::NV][S::NV]) {
+  TH jt[S::NB], jn[S::NB], wt[S::NB], wn[S::NB];
+  const TH ctt = TH(ctt_), cnt = TH(cnt_), cnn = TH(cnn_);
+  static_for<0, S::NB>([&](auto JJ) { constexpr int j = JJ; if constexpr ((SUB >> j) & 1u) { jt[j] = TH(jt_[j]); jn[j] = TH(jn_[j]); wt[j] = ctt * jt[j] + cnt * jn[j]; wn[j] = cnt * jt[j] + cnn * jn[j]; } });
   H[0][0] += ctt; H[1][0] += cnt; H[1][1] += cnn;                       // (ut, un) of the root slides: (1, 0), (0, 1)
   static_for<0, S::NB>([&](auto AA) { constexpr int a = AA;
     if constexpr ((SUB >> a) & 1u) {
@@ -1337,7 +1396,7 @@ REX_HD void list_store(const Constraints<T, S>& C, const LaneParams<T, S>& P, co
     q[LM::off(SF_MU)] = P.mu[g]; });
 }
 template <class T, class S, bool SELF, bool PAIR, bool LAZY = false, int MAXIT = 24>   // LAZY: see solve_newton
-REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
+REX_HD SolveStats solve_newton_list(const hess_t<T, S> (&M)[S::NV][S::NV], const T (&qfrc_smooth)[S::NV], const T (&qacc_smooth)[S::NV],
                                     const Kin<T, S>& K, const Constraints<T, S>& C, unsigned self_mask, const SlotMem<T, S, PAIR>& L,
                                     T (&qacc)[S::NV], bool warm, bool have_a0, int ls_max, int ls_free, int corr) {
   // self_mask: this lane's capsule-capsule rows (their data is in the column: list_store_self); replicated in both lanes of a pair
@@ -1400,18 +1459,24 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
     T fref = T(0);
     static_for<0, S::NV>([&](auto II) { constexpr int i = II; g[i] = Ma[i] - qfrc_smooth[i]; fref += Ma[i] * Ma[i] + qfrc_smooth[i] * qfrc_smooth[i]; });
     unsigned lim_on = 0, e1 = 0, e2 = 0, e3 = 0, self_on = 0;
+    using TH = hess_t<T, S>;   // (planar_spec.hpp: fp64 for the fp32 walker2d, T otherwise)
+    constexpr bool WIDE = !std::is_same_v<TH, T>;   // the Newton system's right-hand side in TH: see solve_newton
+    static_assert(!(WIDE && SELF && S::NSELF > 0), "wide gradient: no capsule-capsule rows");
+    TH gh[WIDE ? S::NV : 1], ghs[WIDE ? S::NV : 1];
+    if constexpr (WIDE) { sym_matvec<T, S>(M, qacc, gh); static_for<0, S::NV>([&](auto II) { gh[II] -= TH(qfrc_smooth[II]); ghs[II] = TH(0); }); }
     static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ;
       if constexpr (S::limited[j]) {
         T jar = C.lsig[j] * qacc[j + 2] - C.laref[j];
         bool on = ((C.lim_mask >> j) & 1u) && jar < T(0);
         if (on) lim_on |= 1u << j;
-        g[j + 2] += on ? C.lsig[j] * C.lD[j] * jar : T(0); } });
-    T Hs[S::NV][S::NV];   // this lane's unit blocks (PAIR: summed over the pair below)
+        g[j + 2] += on ? C.lsig[j] * C.lD[j] * jar : T(0);
+        if constexpr (WIDE) gh[j + 2] += on ? TH(C.lsig[j]) * TH(C.lD[j]) * (TH(C.lsig[j]) * TH(qacc[j + 2]) - TH(C.laref[j])) : TH(0); } });
+    TH Hs[S::NV][S::NV];   // this lane's unit blocks (PAIR: summed over the pair below)
     static_for<0, S::NV>([&](auto II) { constexpr int i = II;
-      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hs[i][j] = T(0); }); });
-    T Hself[(SELF && S::NSELF > 0) ? S::NV : 1][(SELF && S::NSELF > 0) ? S::NV : 1];   // capsule-capsule rows' terms (replicated: NOT summed over the pair)
+      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hs[i][j] = TH(0); }); });
+    TH Hself[(SELF && S::NSELF > 0) ? S::NV : 1][(SELF && S::NSELF > 0) ? S::NV : 1];   // capsule-capsule rows' terms (replicated: NOT summed over the pair)
     if constexpr (SELF && S::NSELF > 0) static_for<2, S::NV>([&](auto II) { constexpr int i = II;
-      static_for<2, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hself[i][j] = T(0); }); });
+      static_for<2, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) Hself[i][j] = TH(0); }); });
     {
       T gs[S::NV];
       static_for<0, S::NV>([&](auto II) { gs[II] = T(0); });
@@ -1431,13 +1496,18 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
           e1 |= s1 ? (1u << b) : 0u; e2 |= s2 ? (1u << b) : 0u; e3 |= s3 ? (1u << b) : 0u;
           const T f1 = s1 ? -D * r1 : T(0), f2 = s2 ? -D * r2 : T(0), f3 = s3 ? -D * r3 : T(0);
           list_accum<T, S, SUB>(jt, jn, -(mu * (f1 - f2)), -(f1 + f2 + T(2) * f3), gs);
+          if constexpr (WIDE) slot_grad_wide<T, S, SUB>(jt, jn, qacc, mu, an, at, D, s1, s2, s3, ghs);
           const T c1 = s1 ? D : T(0), c2 = s2 ? D : T(0), c3 = s3 ? D : T(0);
           list_hess<T, S, SUB>(jt, jn, mu * mu * (c1 + c2), mu * (c1 - c2), c1 + c2 + T(2) * c3, Hs); });
       }
       if constexpr (PAIR) {
         static_for<0, S::NV>([&](auto II) { constexpr int i = II; g[i] += gs[i] + pair_xchg(gs[i]); });
+        if constexpr (WIDE) static_for<0, S::NV>([&](auto II) { constexpr int i = II; gh[i] += ghs[i] + pair_xchg(ghs[i]); });
         e1 |= pair_xchg(e1); e2 |= pair_xchg(e2); e3 |= pair_xchg(e3);
-      } else static_for<0, S::NV>([&](auto II) { constexpr int i = II; g[i] += gs[i]; });
+      } else {
+        static_for<0, S::NV>([&](auto II) { constexpr int i = II; g[i] += gs[i]; });
+        if constexpr (WIDE) static_for<0, S::NV>([&](auto II) { constexpr int i = II; gh[i] += ghs[i]; });
+      }
     }
     if constexpr (SELF && S::NSELF > 0) {   // capsule-capsule rows: gradient and (rank-1) Hessian terms, replicated in both lanes of a pair
       for (unsigned m = ums; m; m &= m - 1u) {
@@ -1456,29 +1526,33 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
         static_for<0, S::NB>([&](auto AA) { constexpr int a = AA;
           g[a + 2] += row[a] * w;
           static_for<0, a + 1>([&](auto BB) { constexpr int bq = BB;
-            if constexpr (dof_coupled<S>(a + 2, bq + 2)) Hself[a + 2][bq + 2] += d * row[a] * row[bq]; }); });
+            if constexpr (dof_coupled<S>(a + 2, bq + 2)) Hself[a + 2][bq + 2] += TH(d) * TH(row[a]) * TH(row[bq]); }); });
       }
     }
     T gn = T(0);
     static_for<0, S::NV>([&](auto II) { gn += g[II] * g[II]; });
     const bool same_set = lim_on == p_lim && e1 == p_e1 && e2 == p_e2 && e3 == p_e3 && self_on == p_self;
     p_lim = lim_on; p_e1 = e1; p_e2 = e2; p_e3 = e3; p_self = self_on;
-    lane_done = lane_done || same_set || !(gn > tol2 * fref);   // NaN counts as done
+    lane_done = lane_done || same_set || grad_at_rounding_level<T, S>(g, Ma, qfrc_smooth, gn, fref, tol2);   // NaN counts as done
     if (!REX_WAVE_ANY(!lane_done)) break;
     REX_COUNT(pass2, 1);
     // ---- Hessian of the current active set, Newton direction ----------------------------------------------------------------------------------
-    T H[S::NV][S::NV];
+    TH H[S::NV][S::NV];
     static_for<0, S::NV>([&](auto II) { constexpr int i = II;
       static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ;
-        if constexpr (dof_coupled<S>(i, j)) { if constexpr (PAIR) H[i][j] = M[i][j] + (Hs[i][j] + pair_xchg(Hs[i][j])); else H[i][j] = M[i][j] + Hs[i][j]; } }); });
+        if constexpr (dof_coupled<S>(i, j)) { if constexpr (PAIR) H[i][j] = TH(M[i][j]) + (Hs[i][j] + pair_xchg(Hs[i][j])); else H[i][j] = TH(M[i][j]) + Hs[i][j]; } }); });
     static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ;
-      if constexpr (S::limited[j]) H[j + 2][j + 2] += ((lim_on >> j) & 1u) ? C.lD[j] : T(0); });
+      if constexpr (S::limited[j]) H[j + 2][j + 2] += TH(((lim_on >> j) & 1u) ? C.lD[j] : T(0)); });
     if constexpr (SELF && S::NSELF > 0) static_for<2, S::NV>([&](auto II) { constexpr int i = II;
       static_for<2, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) H[i][j] += Hself[i][j]; }); });
-    ldl_factor<T, S>(H);
+    ldl_factor<TH, S>(H);
     T sr[S::NV];
-    static_for<0, S::NV>([&](auto II) { sr[II] = -g[II]; });
-    ldl_solve<T, S>(H, sr);
+    {
+      TH sh[S::NV];
+      static_for<0, S::NV>([&](auto II) { if constexpr (WIDE) sh[II] = -gh[II]; else sh[II] = TH(-g[II]); });
+      ldl_solve<TH, S>(H, sh);
+      static_for<0, S::NV>([&](auto II) { sr[II] = T(sh[II]); });
+    }
     if constexpr (SELF && S::NSELF > 0) {   // J sr of the capsule-capsule rows into the column
       for (unsigned m = ums; m; m &= m - 1u) {
         const unsigned r = (unsigned)__builtin_ctz(m);
@@ -1605,7 +1679,7 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
     lane_done = lane_done || exact_step || smax <= stag * (T(1) + amax);
     bool corrected = false;   // (loop tail: see solve_newton)
     // ---- one-group correction (see solve_newton): one joint limit or the edges of ONE unit toggled along a full step ----------------------
-    {
+    if constexpr (!WIDE) {   // (see solve_newton)
       REX_STAT_TOGGLES(lim_on ^ m_lim, (e1 ^ m_e1) | (e2 ^ m_e2) | (e3 ^ m_e3), !lane_done && a == T(1));
 #if defined(__HIP_DEVICE_COMPILE__)
       constexpr int CMODE = PAIR ? 1 : 0;
@@ -1706,10 +1780,11 @@ REX_HD SolveStats solve_newton_list(const T (&M)[S::NV][S::NV], const T (&qfrc_s
 // one forward-dynamics evaluation: qacc(q, v, ctrl)  ([3P] mj_forward)
 // GEN: which code the general solver modes (1, 2) run -- 0 the unrolled per-slot instantiations, 1 the rolled ROW-list solver (the hopper's
 // 256-register two-waves-per-SIMD kernel), 2 the LIST solver (per-unit data in `slot_mem`, this lane's column: LDS on the device)
+// (forward_wide: M in hess_t<T, S>, what substep() keeps between the evaluation and the Euler update; forward() below hands M out in T)
 template <class T, class S, bool PAIR = false, int GEN = 0>
-REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ctrl)[S::NU], const PlanarGeom<T, S>& G,
-                          const LaneParams<T, S>& P, const SolParams<T>& sp, T (&qacc)[S::NV], T (&M)[S::NV][S::NV],
-                          bool warm = false, T* slot_mem = nullptr) {
+REX_HD SolveStats forward_wide(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ctrl)[S::NU], const PlanarGeom<T, S>& G,
+                               const LaneParams<T, S>& P, const SolParams<T>& sp, T (&qacc)[S::NV], hess_t<T, S> (&M)[S::NV][S::NV],
+                               bool warm = false, T* slot_mem = nullptr) {
   constexpr bool ROLLED = GEN == 1;
   // Which instantiations compute the line-search sums lazily (solve_newton, LAZY).  Device: the two-lanes-per-env kernels (feet-only path and list
   // solver).  The one-lane kernels stay eager: the second, sets-only copy of deriv() costs the 458-register hopper kernel registers, and the
@@ -1777,11 +1852,13 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
   // hopper / walker2d step skip this factorisation.
   const bool have_a0 = mode == 0 || !warm || !sp.fast;
   if (have_a0) {
-    T L[S::NV][S::NV];
-    static_for<0, S::NV>([&](auto II) { constexpr int i = II; a0[i] = f[i];
+    using TM = hess_t<T, S>;
+    TM L[S::NV][S::NV], x[S::NV];
+    static_for<0, S::NV>([&](auto II) { constexpr int i = II; x[i] = TM(f[i]);
       static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) L[i][j] = M[i][j]; }); });
-    ldl_factor<T, S>(L);
-    ldl_solve<T, S>(L, a0);
+    ldl_factor<TM, S>(L);
+    ldl_solve<TM, S>(L, x);
+    static_for<0, S::NV>([&](auto II) { a0[II] = T(x[II]); });
   } else static_for<0, S::NV>([&](auto II) { a0[II] = T(0); });
   REX_MARK("dispatch");
   REX_PSTAMP(p_4, a0[0] + T(R.mask));
@@ -1842,6 +1919,21 @@ REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ct
   return st;
 }
 
+template <class T, class S, bool PAIR = false, int GEN = 0>
+REX_HD SolveStats forward(const T (&q)[S::NV], const T (&v)[S::NV], const T (&ctrl)[S::NU], const PlanarGeom<T, S>& G,
+                          const LaneParams<T, S>& P, const SolParams<T>& sp, T (&qacc)[S::NV], T (&M)[S::NV][S::NV],
+                          bool warm = false, T* slot_mem = nullptr) {
+  using TM = hess_t<T, S>;
+  if constexpr (std::is_same_v<TM, T>) return forward_wide<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, qacc, M, warm, slot_mem);
+  else {
+    TM Mw[S::NV][S::NV];
+    const SolveStats st = forward_wide<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, qacc, Mw, warm, slot_mem);
+    static_for<0, S::NV>([&](auto II) { constexpr int i = II;
+      static_for<0, i + 1>([&](auto JJ) { constexpr int j = JJ; if constexpr (dof_coupled<S>(i, j)) M[i][j] = T(Mw[i][j]); }); });
+    return st;
+  }
+}
+
 // one mj_step: RK4 ([3P] mj_RungeKutta, N=4) or semi-implicit Euler with implicit joint damping
 // ([3P] mj_Euler).  Returns the OR of "solver hit its cap".
 template <class T, class S, bool PAIR = false, int GEN = 0>
@@ -1849,7 +1941,8 @@ REX_HD bool substep(T (&q)[S::NV], T (&v)[S::NV], const T (&ctrl)[S::NU], const 
                     const LaneParams<T, S>& P, const SolParams<T>& sp, T (&acc)[S::NV], bool warm, T* slot_mem = nullptr) {
   // acc: in = qacc of the previous evaluation (solver warm start when `warm`), out = qacc of the last one
   const T h = T(S::TIMESTEP);
-  T M[S::NV][S::NV];
+  using TM = hess_t<T, S>;
+  TM M[S::NV][S::NV];
   bool capped = false;
   if constexpr (S::RK4) {
     // stage loop kept rolled: one instance of forward() in the kernel, 4x smaller code and far
@@ -1858,7 +1951,7 @@ REX_HD bool substep(T (&q)[S::NV], T (&v)[S::NV], const T (&ctrl)[S::NU], const 
     static_for<0, S::NV>([&](auto II) { q0[II] = q[II]; v0[II] = v[II]; dq[II] = T(0); dv[II] = T(0); });
 #pragma unroll 1
     for (int stage = 0; stage < 4; ++stage) {
-      capped |= forward<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, M, sp.warm && (warm || stage > 0), slot_mem).capped;
+      capped |= forward_wide<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, M, sp.warm && (warm || stage > 0), slot_mem).capped;
       const T w = (stage == 0 || stage == 3) ? T(1.0 / 6) : T(1.0 / 3);   // B = [1/6 1/3 1/3 1/6]
       const T c = stage == 2 ? h : T(0.5) * h;                             // A = [.5; 0 .5; 0 0 1]
       static_for<0, S::NV>([&](auto II) { constexpr int i = II;
@@ -1869,13 +1962,15 @@ REX_HD bool substep(T (&q)[S::NV], T (&v)[S::NV], const T (&ctrl)[S::NU], const 
     }
   } else {
     T rhs[S::NV];
-    capped |= forward<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, M, sp.warm && warm, slot_mem).capped;
+    capped |= forward_wide<T, S, PAIR, GEN>(q, v, ctrl, G, P, sp, acc, M, sp.warm && warm, slot_mem).capped;
     // (M + h*diag(damping)) a = qfrc_smooth + qfrc_constraint = M qacc
     sym_matvec<T, S>(M, acc, rhs);
-    static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ; M[j + 2][j + 2] += h * G.damping[j]; });
-    ldl_factor<T, S>(M);
-    ldl_solve<T, S>(M, rhs);
-    static_for<0, S::NV>([&](auto II) { constexpr int i = II; v[i] += h * rhs[i]; q[i] += h * v[i]; });
+    static_for<1, S::NB>([&](auto JJ) { constexpr int j = JJ; M[j + 2][j + 2] += TM(h * G.damping[j]); });
+    ldl_factor<TM, S>(M);
+    TM rh[S::NV];
+    static_for<0, S::NV>([&](auto II) { rh[II] = TM(rhs[II]); });
+    ldl_solve<TM, S>(M, rh);
+    static_for<0, S::NV>([&](auto II) { constexpr int i = II; v[i] += h * T(rh[i]); q[i] += h * v[i]; });
   }
   return capped;
 }

@@ -6,6 +6,7 @@
 // line is next to each value.  The trees are planar: slide-x, slide-z, hinge-y root followed by
 // hinges about +/-y, so the kernels work with 2-D (x,z) vectors and one angle per body.
 #pragma once
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -75,6 +76,11 @@ template <class T> REX_HD void opaque(T& x) {
 REX_HD unsigned pair_parity() { return threadIdx.x & 1u; }
 REX_HD float pair_xchg(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true)); }
 REX_HD unsigned pair_xchg(unsigned x) { return (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); }
+REX_HD double pair_xchg(double x) {   // (the wide Hessian of hess_t below: one DPP move per half)
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = pair_xchg((unsigned)u), hi = pair_xchg((unsigned)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 #else
 inline unsigned pair_parity() { return 0u; }
 template <class T> inline T pair_xchg(T x) { return x; }   // PAIR is never instantiated on the host
@@ -127,6 +133,7 @@ struct HopperSpec {
   static constexpr float INIT_NOISE = 0.005f;                       // random_hopper.py:113-114
   static constexpr bool DR_BEFORE_STATE = false;                    // random_hopper.py:113-118
   static constexpr unsigned FAST_SLOTS = 0xC0u;                     // both ends of the foot capsule (slot = 2 * geom + end)
+  static constexpr bool WIDE_HESSIAN = false;                       // see hess_t
 };
 
 struct Walker2dSpec {
@@ -153,6 +160,7 @@ struct Walker2dSpec {
   static constexpr float INIT_NOISE = 0.005f;                       // random_walker2d.py:148-151
   static constexpr bool DR_BEFORE_STATE = true;                     // random_walker2d.py:145-151
   static constexpr unsigned FAST_SLOTS = (3u << 6) | (3u << 12);    // the two foot capsules (geoms 3 and 6)
+  static constexpr bool WIDE_HESSIAN = true;                        // per-env link lengths beside per-env masses: see hess_t
 };
 
 struct HalfCheetahSpec {
@@ -179,7 +187,19 @@ struct HalfCheetahSpec {
   static constexpr float INIT_NOISE = 0.1f;                         // random_half_cheetah.py:124-125
   static constexpr bool DR_BEFORE_STATE = false;
   static constexpr unsigned FAST_SLOTS = (3u << 8) | (3u << 14);    // bfoot and ffoot (geoms 4 and 7)
+  static constexpr bool WIDE_HESSIAN = false;                       // see hess_t
 };
+
+// Scalar type the Newton solver keeps the joint-space inertia M, the Hessian H = M + J^T D J, its L^T D L factors and the right-hand side of
+// the Newton system in.  D is the inverse of a regularisation sized from the NOMINAL model's inverse weights, so the stiff part J^T D J
+// outweighs M by |J|^2 D / M, and M -- which alone decides the acceleration along the directions the active rows leave free -- survives
+// forming and eliminating H in fp32 only to eps_fp32 times that ratio.  With the masses AND the link lengths of the model per env (walker2d:
+// a 0.5 kg, 15 cm link under a regularisation derived for its length but the nominal masses) the "exact" Newton step of a converged active
+// set was several per cent off at the corners of the search box, and M itself, rounded to fp32 entries, moved M^-1 f by 3e-4
+// (profiles/HISTORY.md, "walker2d wide solve").  Products of two fp32 values are exact in fp64, so there H carries M to full fp32 precision.
+// The kinds with uniform geometry hold the tolerance over their boxes in T (tests/test_planar_box_host.py) and keep it: their kernels and
+// their arithmetic do not change.
+template <class T, class S> using hess_t = std::conditional_t<S::WIDE_HESSIAN && sizeof(T) == 4, double, T>;
 
 // compile-time tree helpers --------------------------------------------------------------
 template <class S>

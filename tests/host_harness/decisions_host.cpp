@@ -4,6 +4,7 @@
 // records and tests/test_wave_decisions_host.py replays.  Besides the stepped state it reports, per env, the solver instantiation that one
 // forward() at the start state enters (SolveStats::mode), so the fixture can show which paths its inputs reach.
 #include "../../random-envs_amd/csrc/planar_model.hpp"
+#include "walker_derive_host.hpp"
 
 using namespace rex;
 
@@ -21,7 +22,7 @@ static void dh_run(int n, int nsub, const DhKnobs& kn, const float* qpos, const 
     for (int k = 0; k < S::NV; k++) { q[k] = qpos[(size_t)i * S::NV + k]; v[k] = qvel[(size_t)i * S::NV + k]; }
     for (int k = 0; k < S::NU; k++) c[k] = act[(size_t)i * S::NU + k];
     for (int k = 0; k < S::NXI; k++) x[k] = xi[(size_t)i * S::NXI + k];
-    if (S::KIND == 3) { T s4[4] = {x[7], x[8], x[9], x[10]}; derive_model<T, S>(s4, G, nominal, sp); }   // walker: geometry from the xi lengths
+    if constexpr (S::KIND == 3) walker_geom_like_device<T>(x, G);   // walker: geometry from the xi lengths
     if (kn.fast >= 0) sp.fast = kn.fast;
     if (kn.corr >= 0) sp.corr = kn.corr;
     if (kn.warm >= 0) sp.warm = kn.warm;

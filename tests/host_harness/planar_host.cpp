@@ -5,6 +5,7 @@
 // Python package only ever calls librex_hip.so.
 #include <cstring>
 #include "../../random-envs_amd/csrc/planar_model.hpp"
+#include "walker_derive_host.hpp"
 
 using namespace rex;
 
@@ -29,10 +30,7 @@ static void run_step(int n, int nsub, const double* qpos, const double* qvel, co
     for (int k = 0; k < S::NV; k++) { q[k] = T(qpos[(size_t)k * n + i]); v[k] = T(qvel[(size_t)k * n + i]); }
     for (int k = 0; k < S::NU; k++) c[k] = T(act[(size_t)k * n + i]);
     for (int k = 0; k < S::NXI; k++) x[k] = T(xi[(size_t)k * n + i]);
-    if (S::KIND == 3) {  // walker: geometry from the xi lengths
-      T s4[4] = {x[7], x[8], x[9], x[10]};
-      derive_model<T, S>(s4, G, nominal, sp);
-    }
+    if constexpr (S::KIND == 3) walker_geom_like_device<T>(x, G);   // walker: geometry from the xi lengths
     sp.fast = g_fast; if (g_ls_max >= 0) sp.ls_max = g_ls_max; if (g_ls_free >= 0) sp.ls_free = g_ls_free;
     LaneParams<T, S> P; lane_params(S{}, x, P);
     bool cap = false; T acc[S::NV];
@@ -53,8 +51,8 @@ static void run_forward(const double* qpos, const double* qvel, const double* ac
   for (int k = 0; k < S::NV; k++) { q[k] = T(qpos[k]); v[k] = T(qvel[k]); }
   for (int k = 0; k < S::NU; k++) c[k] = T(act[k]);
   for (int k = 0; k < S::NXI; k++) x[k] = T(xi[k]);
-  if (S::KIND == 3) { sz[0] = x[7]; sz[1] = x[8]; sz[2] = x[9]; sz[3] = x[10]; }
   derive_model<T, S>(sz, G, nominal, sp);
+  if constexpr (S::KIND == 3) walker_geom_like_device<T>(x, G);
   sp.fast = g_fast; if (g_ls_max >= 0) sp.ls_max = g_ls_max; if (g_ls_free >= 0) sp.ls_free = g_ls_free;
   LaneParams<T, S> P; lane_params(S{}, x, P);
   for (int i = 0; i < S::NV; i++) for (int j = 0; j < S::NV; j++) M[i][j] = T(0);

@@ -215,3 +215,39 @@ def rollout_states(kind, n, steps_max=60, seed=0, xi_scale=(0.7, 1.3), nthreads=
         out = oracle_batch_step(kind, q[idx], v[idx], act[idx], xi[idx], nthreads=nthreads, tolerance=0.0)
         q[idx] = out["qpos"]; v[idx] = out["qvel"]
     return q, v, xi
+
+
+def box_states(kind, n, mode, seed, steps_max=60, nthreads=8, variant=0):
+    """(qpos, qvel, xi) with xi over the WHOLE search box of `kind` (SPECS[kind].search_bounds; variant=1: the Unmodeled id's reduced
+    task over UNMODELED_SPECS[kind].search_bounds): mode "uniform" draws every
+    component from U(lo, hi), "corners" sets every component independently to lo or hi.  States are sampled along oracle rollouts
+    of 0 .. steps_max - 1 steps under U(-1, 1) actions from the reset distribution, and the rollouts honour the done rule: a lane
+    whose step reports done restarts from a fresh reset state (so no lane is a fallen robot the product would never step).
+    Deterministic for a given (kind, n, mode, seed, steps_max)."""
+    from random_envs_amd.specs import SPECS, UNMODELED_SPECS
+    assert mode in ("uniform", "corners")
+    d = DIMS[kind]; rng = np.random.RandomState(seed)
+    bounds = (UNMODELED_SPECS if variant else SPECS)[kind].search_bounds
+    nx = UNMODELED_NX[kind] if variant else d["nx"]
+    lo = np.array([b[0] for b in bounds], dtype=np.float64); hi = np.array([b[1] for b in bounds], dtype=np.float64)
+    assert lo.shape == (nx,)
+    xi = rng.uniform(lo, hi, (n, nx)) if mode == "uniform" else np.where(rng.rand(n, nx) < 0.5, lo, hi)
+
+    def reset_states(m):
+        if kind == "halfcheetah":
+            return rng.uniform(-0.1, 0.1, (m, d["nq"])), 0.1 * rng.randn(m, d["nv"])
+        q = rng.uniform(-0.005, 0.005, (m, d["nq"])); q[:, 1] += 1.25
+        return q, rng.uniform(-0.005, 0.005, (m, d["nv"]))
+
+    q, v = reset_states(n)
+    steps = rng.randint(0, steps_max, n)
+    for s in range(int(steps.max())):
+        act = rng.uniform(-1, 1, (n, d["nu"]))
+        idx = np.where(steps > s)[0]
+        out = oracle_batch_step(kind, q[idx], v[idx], act[idx], xi[idx], nthreads=nthreads, tolerance=0.0, variant=variant)
+        q[idx] = out["qpos"]; v[idx] = out["qvel"]
+        fell = idx[out["done"]]
+        if fell.size:
+            q[fell], v[fell] = reset_states(fell.size)
+    assert np.isfinite(q).all() and np.isfinite(v).all()
+    return q, v, xi
