@@ -542,6 +542,56 @@ int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_b
                          float* reward_out, float* done_out, float* discount_out, int32_t* steps_out, int64_t* index_out, float* prob_out,
                          void* stream);
 
+/* ---- sequence windows sampled from the replay buffer -------------------------------------------------------------------------------
+ * The sequence variant of rex_rbuf_sample / rex_rbuf_gather / rex_per_sample, which stay as they are: what a recurrent actor / critic
+ * (R2D2, recurrent SAC / TD3) or a network fed a history of observations and actions (RMA's adaptation module, UP-OSI, sequence models)
+ * trains on -- up to L consecutive steps of one env behind every id, cut at the episode's end, zero-padded, with a validity mask --
+ * copied inside one launch.  Storage, handle, rex_rbuf_enable and the rules of the family are those of rex_rbuf_*: REX_ERR_STATE before
+ * rex_rbuf_enable, no allocation, no synchronisation, no host state between calls, n == 0 does nothing.
+ *
+ * New argument: seq_len = L, an int in [1, 64]; head, an int64 in [0, T), is the slot written most recently, as in the n-step calls.
+ * Anything else is REX_ERR_ARG.
+ *
+ * Sample j has the guarded id s, with t0 = s / B and b = s % B.  Its window is the steps k = 0, 1, ... with t_k = (t0 + k) mod T and
+ * s_k = t_k * B + b.  Step k is the LAST step of the window (so m = k + 1) when the first of these holds -- the n-step rule with n_step
+ * replaced by L:
+ *   done[s_k] != 0 || timeout[s_k] != 0   the episode ends there;
+ *   t_k == head                           the next slot holds the oldest data of a full ring, or nothing at all;
+ *   k == L - 1.
+ * Outputs, batch-first, each optional (NULL skips; a skipped buffer is left untouched):
+ *   obs_out    [n][L+1][obs_dim] f32           row k < m: the obs row of s_k; row m: the next_obs row of s_(m-1), the observation to
+ *                                              bootstrap from; rows > m: zeros.  obs_out[:, :-1] and obs_out[:, 1:] are then obs and
+ *                                              next_obs of every valid step
+ *   action_out [n][L][act_dim] 4-byte words    row k < m: the action row of s_k, bit for bit; else zeros
+ *   reward_out [n][L] f32                      reward[s_k] for k < m, else 0
+ *   done_out   [n][L] f32                      (done[s_k] && !timeout[s_k]) ? 1 : 0 for k < m, else 0
+ *   mask_out   [n][L] f32                      1 for k < m, else 0
+ *   length_out [n] int32                       m
+ *   index_out  [n] int64                       s, in the sampling calls
+ * The launch writes the padding zeros itself: the outputs need no initialisation.
+ * normalise != 0 behaves as in rex_rbuf_sample (REX_ERR_STATE without rex_norm_enable): with norm_obs every written row of obs_out, row m
+ * included, is normalised with its column's statistic and the padding stays zero; with norm_reward each term of reward_out is normalised
+ * as rex_rbuf_sample normalises a reward; done_out, mask_out, length_out and action_out are never normalised.  Under frozen statistics a
+ * normalised row of a window equals the normalised row rex_rbuf_gather returns for the same id, bit for bit.
+ * An id outside [0, T * B) is never turned into an address: every output of that sample is zero, length_out included, and it is counted
+ * in the counter rex_rbuf_read_bad_indices reads.
+ * With seq_len == 1, obs_out[:, 0], obs_out[:, 1], action_out[:, 0], reward_out[:, 0] and done_out[:, 0] are bit-identical to the five
+ * outputs of rex_rbuf_gather, for any head. */
+/* ONE launch over the caller's ids: index [dev, int64 n]. */
+int rex_rbuf_gather_seq(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int64_t head, int seq_len, int normalise,
+                        float* obs_out, void* action_out, float* reward_out, float* done_out, float* mask_out, int32_t* length_out,
+                        void* stream);
+/* ONE launch.  The ids are exactly those of rex_rbuf_sample for the same (seed, draw, size, B, j); every stored id is a valid start,
+ * because the window shortens instead.  size / head are validated as in rex_rbuf_sample_nstep. */
+int rex_rbuf_sample_seq(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t head, int64_t n, uint64_t seed, uint64_t draw,
+                        int seq_len, int normalise, float* obs_out, void* action_out, float* reward_out, float* done_out, float* mask_out,
+                        int32_t* length_out, int64_t* index_out, void* stream);
+/* TWO launches: the unchanged launch of rex_per_draw, then the sequence launch over index_out (needs rex_per_enable too, and the same T
+ * in both descriptions).  An id of -1 meets the guard: zeros, counted. */
+int rex_per_sample_seq(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_buffers* per, int64_t n, int64_t head, uint64_t seed,
+                       uint64_t draw, int seq_len, int normalise, float* obs_out, void* action_out, float* reward_out, float* done_out,
+                       float* mask_out, int32_t* length_out, int64_t* index_out, float* prob_out, void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

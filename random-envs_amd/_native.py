@@ -26,6 +26,7 @@ SYMBOLS = [
     "rex_per_tree_len", "rex_per_enable", "rex_per_init", "rex_per_add", "rex_per_update", "rex_per_rebuild", "rex_per_draw", "rex_per_sample",
     "rex_per_read_counters",
     "rex_rbuf_gather_nstep", "rex_rbuf_sample_nstep", "rex_per_sample_nstep",
+    "rex_rbuf_gather_seq", "rex_rbuf_sample_seq", "rex_per_sample_seq",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -156,6 +157,9 @@ def lib():
     L.rex_rbuf_gather_nstep.argtypes = [vp, rp, vp, i64, i64, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_rbuf_sample_nstep.argtypes = [vp, rp, i64, i64, i64, u64, u64, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_per_sample_nstep.argtypes = [vp, rp, pp, i64, i64, u64, u64, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rbuf_gather_seq.argtypes = [vp, rp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rbuf_sample_seq.argtypes = [vp, rp, i64, i64, i64, u64, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_per_sample_seq.argtypes = [vp, rp, pp, i64, i64, u64, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

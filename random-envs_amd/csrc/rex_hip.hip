@@ -39,6 +39,7 @@
 #include "replay_buffer.hpp"
 #include "priority_replay.hpp"
 #include "nstep_replay.hpp"
+#include "seq_replay.hpp"
 #include "eplog.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
@@ -1293,23 +1294,27 @@ extern "C" int rex_rbuf_add(rex_t* h, const rex_rbuf_buffers* buf, int64_t t, co
 }
 
 // The one launch path of the sample family -- rex_rbuf_sample / _gather / rex_per_sample through rb_sample_kernel, their _nstep forms
-// through rb_nstep_kernel: `p` is what the kernel takes, `s` the rbuf::SampleParams inside it (p itself for the plain kernel)
+// through rb_nstep_kernel, their _seq forms through rb_seq_kernel (a grid of two dimensions, `grid_y`): `p` is what the kernel takes, `s` the
+// rbuf::SampleParams inside it (p itself for the plain kernel)
 template <class P>
-static int launch_sample(const rex_env* h, const char* fn, void (*kernel)(P), P& p, rbuf::SampleParams& s, int normalise, void* stream) {
+static int launch_sample(const rex_env* h, const char* fn, void (*kernel)(P), P& p, rbuf::SampleParams& s, int normalise, void* stream,
+                         long long (*grid_y)(P&) = nullptr) {
   if (normalise) {
     if (!h->norm_mem) return set_err(REX_ERR_STATE, "%s: normalise needs rex_norm_enable on this handle", fn);
     const rex_norm_config& c = h->norm_cfg;
     s.norm = rbuf::Norm{h->norm.stats, h->norm.rows, c.norm_obs ? 1 : 0, c.norm_reward ? 1 : 0, c.epsilon, c.clip_obs, c.clip_reward};
   }
   if (s.n == 0) return REX_OK;
-  const long long blocks = rbuf::sample_blocks(s.n);
+  const long long blocks = grid_y ? s.n : rbuf::sample_blocks(s.n);   // a kernel with a grid of two dimensions takes a block row per sample
   if (!grid_fits(blocks)) return set_err(REX_ERR_ARG, "%s: n = %lld is more than one launch takes", fn, s.n);
   // 16-byte accesses: with dim a multiple of 4 every row of a 16-byte aligned buffer starts 16-byte aligned
   const rbuf::Buf& b = s.buf;
   s.vec_obs = (b.obs_dim % 4 == 0 && postpass::all_aligned16(b.obs, b.next_obs, s.out.obs, s.out.next_obs)) ? 1 : 0;
   s.vec_act = (b.act_dim % 4 == 0 && postpass::all_aligned16(b.action, s.out.action)) ? 1 : 0;
   s.bad = (unsigned long long*)h->rbuf_mem;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(rbuf::BLOCK), 0, (hipStream_t)stream, p);
+  const long long rows = grid_y ? grid_y(p) : 1;                       // ... and says how many blocks serve it, once the access widths are known
+  if (rows > 65535) return set_err(REX_ERR_ARG, "%s: a sample of %lld blocks is more than one launch takes", fn, rows);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(rbuf::BLOCK), 0, (hipStream_t)stream, p);
   HIP_TRY(hipGetLastError());
   return REX_OK;
 }
@@ -1581,4 +1586,67 @@ extern "C" int rex_per_sample_nstep(rex_t* h, const rex_rbuf_buffers* rb, const 
   p.s.out = rbuf_out(obs_out, next_obs_out, action_out, reward_out, done_out, nullptr);
   p.discount = discount_out; p.steps = steps_out;
   return launch_sample(h, "rex_per_sample_nstep", nstep::rb_nstep_kernel, p, p.s, normalise, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// sequence windows from the replay buffer (seq_replay.hpp): the sample / gather launch with up to 64 consecutive steps copied behind every id
+// ------------------------------------------------------------------------------------------
+// the window arguments every sequence call takes
+static int seq_win(const char* fn, const rbuf::Buf& b, int64_t head, int seq_len, seq::Win* out) {
+  if (seq_len < 1 || seq_len > seq::MAX_LEN) return set_err(REX_ERR_ARG, "%s: seq_len %d outside [1, %d]", fn, seq_len, seq::MAX_LEN);
+  if (head < 0 || head >= b.T) return set_err(REX_ERR_ARG, "%s: head %lld outside [0, %lld)", fn, (long long)head, b.T);
+  *out = seq::Win{(long long)head, seq_len};
+  return REX_OK;
+}
+// the outputs (obs_out holds the next_obs row too) and the launch: the steps of a thread follow the access widths launch_sample settles
+static long long seq_grid_y(seq::Params& p) { seq::set_steps(&p); return seq::chunks(p); }
+static int launch_seq(const rex_env* h, const char* fn, seq::Params& p, int normalise, float* obs_out, void* action_out, float* reward_out,
+                      float* done_out, float* mask_out, int32_t* length_out, int64_t* index_out, void* stream) {
+  p.s.out = rbuf_out(obs_out, nullptr, action_out, reward_out, done_out, index_out);
+  p.mask = mask_out; p.length = length_out;
+  return launch_sample(h, fn, seq::rb_seq_kernel, p, p.s, normalise, stream, seq_grid_y);
+}
+
+extern "C" int rex_rbuf_gather_seq(rex_t* h, const rex_rbuf_buffers* buf, const int64_t* index, int64_t n, int64_t head, int seq_len, int normalise,
+                                   float* obs_out, void* action_out, float* reward_out, float* done_out, float* mask_out, int32_t* length_out,
+                                   void* stream) {
+  REX_ENTER(h, "rex_rbuf_gather_seq");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_gather_seq", "rex_rbuf_enable");
+  seq::Params p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_gather_seq", &p.s.buf)) return rc;
+  if (int rc = seq_win("rex_rbuf_gather_seq", p.s.buf, head, seq_len, &p.win)) return rc;
+  if (int rc = check_gather("rex_rbuf_gather_seq", index, n)) return rc;
+  p.s.index = (const long long*)index; p.s.n = n; p.s.N = p.s.buf.T * p.s.buf.B;
+  return launch_seq(h, "rex_rbuf_gather_seq", p, normalise, obs_out, action_out, reward_out, done_out, mask_out, length_out, nullptr, stream);
+}
+
+extern "C" int rex_rbuf_sample_seq(rex_t* h, const rex_rbuf_buffers* buf, int64_t size, int64_t head, int64_t n, uint64_t seed, uint64_t draw,
+                                   int seq_len, int normalise, float* obs_out, void* action_out, float* reward_out, float* done_out,
+                                   float* mask_out, int32_t* length_out, int64_t* index_out, void* stream) {
+  REX_ENTER(h, "rex_rbuf_sample_seq");
+  REX_NEEDS(h, rbuf_mem, "rex_rbuf_sample_seq", "rex_rbuf_enable");
+  seq::Params p{};
+  if (int rc = rbuf_buf(h, buf, "rex_rbuf_sample_seq", &p.s.buf)) return rc;
+  if (int rc = seq_win("rex_rbuf_sample_seq", p.s.buf, head, seq_len, &p.win)) return rc;
+  if (int rc = check_size("rex_rbuf_sample_seq", size, buf->T)) return rc;
+  if (size < buf->T && head != size - 1)
+    return set_err(REX_ERR_ARG, "rex_rbuf_sample_seq: a ring that is not full (size %lld < %lld) has head == size - 1, not %lld", (long long)size,
+                   (long long)buf->T, (long long)head);
+  if (int rc = check_n("rex_rbuf_sample_seq", n)) return rc;
+  p.s.n = n; p.s.N = (long long)size * h->B; p.s.seed = seed; p.s.draw = draw;
+  return launch_seq(h, "rex_rbuf_sample_seq", p, normalise, obs_out, action_out, reward_out, done_out, mask_out, length_out, index_out, stream);
+}
+
+extern "C" int rex_per_sample_seq(rex_t* h, const rex_rbuf_buffers* rb, const rex_per_buffers* buf, int64_t n, int64_t head, uint64_t seed, uint64_t draw,
+                                  int seq_len, int normalise, float* obs_out, void* action_out, float* reward_out, float* done_out, float* mask_out,
+                                  int32_t* length_out, int64_t* index_out, float* prob_out, void* stream) {
+  REX_ENTER(h, "rex_per_sample_seq");
+  REX_NEEDS(h, per_mem, "rex_per_sample_seq", "rex_per_enable");
+  REX_NEEDS(h, rbuf_mem, "rex_per_sample_seq", "rex_rbuf_enable");
+  per::Buf b;
+  seq::Params p{};
+  if (int rc = per_pair(h, "rex_per_sample_seq", rb, buf, &b, &p.s.buf)) return rc;
+  if (int rc = seq_win("rex_per_sample_seq", p.s.buf, head, seq_len, &p.win)) return rc;
+  if (int rc = per_draw_ids(h, "rex_per_sample_seq", b, n, seed, draw, normalise, index_out, prob_out, stream, &p.s)) return rc;
+  return launch_seq(h, "rex_per_sample_seq", p, normalise, obs_out, action_out, reward_out, done_out, mask_out, length_out, nullptr, stream);
 }

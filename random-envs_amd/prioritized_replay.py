@@ -67,6 +67,14 @@ class PrioritizedReplayBuffer(ReplayBuffer):
             raise RuntimeError("PrioritizedReplayBuffer.sample_nstep: the buffer is empty")
         return self._with_weight(self._launch(int(batch_size), None, (n_step, gamma), normalize, ctypes.byref(self._per)), beta)
 
+    def sample_seq(self, batch_size, seq_len, beta=None, normalize=None):
+        """:meth:`sample` with the sequence window of :meth:`ReplayBuffer.sample_seq` behind every id, in two launches: the same draw
+        (``index`` and ``prob`` are those :meth:`sample` returns at the same draw number), then the sequence launch over its ids.  The
+        dict of :meth:`ReplayBuffer.sample_seq` plus ``prob`` and ``weight``."""
+        if len(self) == 0:
+            raise RuntimeError("PrioritizedReplayBuffer.sample_seq: the buffer is empty")
+        return self._with_weight(self._launch(int(batch_size), None, int(seq_len), normalize, ctypes.byref(self._per)), beta)
+
     def update_priorities(self, index, td_error):
         """Priority of transition ``index[j]`` <- ``(|td_error[j]| + eps) ** alpha`` (float32, computed by torch: a device ``powf`` would
         put a transcendental's rounding into the bit-exact contract).  ``index`` int64 [n] and ``td_error`` float32 [n] on the

@@ -8,7 +8,8 @@ of ``n_slots`` time slots over the env's batch, TRANSITION-MAJOR (``obs`` / ``ne
 minibatch on the device (Philox4x32-10, no host randomness, no synchronisation) and copies the whole rows into the row-major
 ``[n, dim]`` layout a network reads, normalised with the running statistics of a ``NormalizedVecRandomEnv`` on request
 (``rex_rbuf_*`` of include/rex.h, csrc/replay_buffer.hpp).  ``sample_nstep`` / ``gather_nstep`` form an n-step return behind every id
-in the same single launch (csrc/nstep_replay.hpp).
+in the same single launch (csrc/nstep_replay.hpp); ``sample_seq`` / ``gather_seq`` copy a window of consecutive steps behind every id,
+padded and masked, in one launch too (csrc/seq_replay.hpp).
 """
 import ctypes
 
@@ -73,33 +74,50 @@ class ReplayBuffer(Layer):
             self.pos, self.full = 0, True
 
     # ------------------------------------------------------------------ learn
-    def _launch(self, n, index, nstep, normalize, per=None):
+    def _launch(self, n, index, window, normalize, per=None):
         """The one call site of the sample family.  ``index`` None: the ids are drawn (``draws`` goes up), uniformly, or by the priorities
-        behind ``per`` (a :class:`PrioritizedReplayBuffer`'s description, by reference); else they are gathered.  ``nstep``: None or
-        ``(n_step, gamma)``.  Allocates and returns the output dict.  The five pointers every entry point takes are formed once; each call
-        below names the entry point's own extra outputs beside them, in the order of include/rex.h."""
+        behind ``per`` (a :class:`PrioritizedReplayBuffer`'s description, by reference); else they are gathered.  ``window``: None, the
+        ``(n_step, gamma)`` of an n-step return, or the int ``seq_len`` of a sequence.  Allocates and returns the output dict.  The
+        pointers every entry point of a kind takes are formed once; each call below names the entry point's own extra outputs beside
+        them, in the order of include/rex.h."""
         t, dev, p, L = self._torch, self.device, self._p, self._L
         f32 = t.float32
-        obs, nxt = t.empty(n, self.obs_dim, dtype=f32, device=dev), t.empty(n, self.obs_dim, dtype=f32, device=dev)
-        act = t.empty(n, self.act_dim, dtype=self.action.dtype, device=dev)
-        rew, done = t.empty(n, dtype=f32, device=dev), t.empty(n, dtype=f32, device=dev)
-        out = {"obs": obs, "next_obs": nxt, "action": act, "reward": rew, "done": done}
-        five = (p(obs), p(nxt), p(act), p(rew), p(done))
+        seq = isinstance(window, int)
+        obs_rows, rows = ((window + 1,), (window,)) if seq else ((), ())     # a sequence: [n, L + 1] observation rows, [n, L] of the rest
+        obs = t.empty(n, *obs_rows, self.obs_dim, dtype=f32, device=dev)
+        act = t.empty(n, *rows, self.act_dim, dtype=self.action.dtype, device=dev)
+        rew, done = t.empty(n, *rows, dtype=f32, device=dev), t.empty(n, *rows, dtype=f32, device=dev)
+        if seq:
+            mask, length = t.empty(n, window, dtype=f32, device=dev), t.empty(n, dtype=t.int32, device=dev)
+            out = {"obs": obs, "action": act, "reward": rew, "done": done, "mask": mask, "length": length}
+            outs = (p(obs), p(act), p(rew), p(done), p(mask), p(length))
+        else:
+            nxt = t.empty(n, self.obs_dim, dtype=f32, device=dev)
+            out = {"obs": obs, "next_obs": nxt, "action": act, "reward": rew, "done": done}
+            five = (p(obs), p(nxt), p(act), p(rew), p(done))
         h, desc, norm, stream = self._h, ctypes.byref(self._desc), self._normalise_flag(normalize), self._stream()
         if index is None:
             ids = out["index"] = t.empty(n, dtype=t.int64, device=dev)
             size, seed, draw = self.n_slots if self.full else self.pos, self.seed, self.draws
             if per is not None:
                 prob = out["prob"] = t.empty(n, dtype=f32, device=dev)
-        if nstep is None:
+        if window is None:
             if index is not None:
                 rc = L.rex_rbuf_gather(h, desc, p(index), n, norm, *five, stream)
             elif per is None:
                 rc = L.rex_rbuf_sample(h, desc, size, n, seed, draw, norm, *five, p(ids), stream)
             else:
                 rc = L.rex_per_sample(h, desc, per, n, seed, draw, norm, *five, p(ids), p(prob), stream)
+        elif seq:
+            head = self._head()
+            if index is not None:
+                rc = L.rex_rbuf_gather_seq(h, desc, p(index), n, head, window, norm, *outs, stream)
+            elif per is None:
+                rc = L.rex_rbuf_sample_seq(h, desc, size, head, n, seed, draw, window, norm, *outs, p(ids), stream)
+            else:
+                rc = L.rex_per_sample_seq(h, desc, per, n, head, seed, draw, window, norm, *outs, p(ids), p(prob), stream)
         else:
-            head, n_step, gamma = self._head(), int(nstep[0]), float(nstep[1])
+            head, n_step, gamma = self._head(), int(window[0]), float(window[1])
             disc = out["discount"] = t.empty(n, dtype=f32, device=dev)
             steps = out["steps"] = t.empty(n, dtype=t.int32, device=dev)
             if index is not None:
@@ -153,6 +171,26 @@ class ReplayBuffer(Layer):
         and ``steps`` included) and is counted (:meth:`bad_indices`)."""
         self._check_index(index)
         return self._launch(index.numel(), index, (n_step, gamma), normalize)
+
+    # ------------------------------------------------------------------ learn, sequences
+    def sample_seq(self, batch_size, seq_len, normalize=None):
+        """:meth:`sample` with a window of up to ``seq_len`` (1 .. 64) consecutive steps of the same env behind every id, still in ONE
+        launch: what a recurrent or history-fed learner trains on.  The window follows the env through the ring and ends early at a
+        done, a time limit or the newest slot (the rule of :meth:`sample_nstep`); ``length`` [n] int32 is its number of steps ``m``.
+        Batch-first: ``obs`` [n, L + 1, obs_dim] holds the observations of the steps and, in row ``m``, the observation to bootstrap
+        from (``obs[:, :-1]`` / ``obs[:, 1:]`` are obs / next_obs of every valid step); ``action`` [n, L, act_dim]; ``reward``, ``done``
+        (``done and not timeout``) and ``mask`` (1 on the valid steps) [n, L] float32; ``index`` [n] int64.  Everything past a window's
+        end is zero.  The ids are those :meth:`sample` draws at the same draw number, and the methods share that number.  With
+        ``normalize`` the written observation rows and every reward are normalised as :meth:`sample` normalises them."""
+        if self.pos == 0 and not self.full:
+            raise RuntimeError("ReplayBuffer.sample_seq: the buffer is empty")
+        return self._launch(int(batch_size), None, int(seq_len), normalize)
+
+    def gather_seq(self, index, seq_len, normalize=None):
+        """The same launch for the caller's ids, as :meth:`gather` is to :meth:`sample`.  An id out of range gives zeros (``length``
+        included) and is counted (:meth:`bad_indices`)."""
+        self._check_index(index)
+        return self._launch(index.numel(), index, int(seq_len), normalize)
 
     def bad_indices(self, clear=True):
         """Ids out of range the gathers met since the last clearing read (their outputs are zeros).  Synchronises."""
