@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Render the reference's MJCF templates (build container only) and commit what they SAY as data:
-tests/golden/mjcf_tables.json.  The templates are rendered with plain jinja2 exactly as
+tests/golden/mjcf_tables.json, and walker2d at further `size` vectors (the two corners of the length search box and
+three seeded interior points) as tests/golden/mjcf_tables_walker_sizes.json.  The templates are rendered with plain jinja2 exactly as
 random_envs/jinja/template_renderer.py:16-19 does (size=..., sin, cos, pi) and parsed with ElementTree;
 defaults classes are resolved for joints / geoms / motors; everything is converted to WORLD coordinates at
 qpos0 so the oracle's and the kernels' model builders can be checked against it element by element."""
@@ -13,6 +14,8 @@ import numpy as np
 REF = os.environ.get("REX_REFERENCE", "/root/reference")
 ASSETS = os.path.join(REF, "random_envs", "jinja", "assets")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mjcf_tables.json")
+OUT_SIZES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mjcf_tables_walker_sizes.json")
+WALKER_LENGTH_BOX = (0.15, 1.0)          # random_walker2d.py:56-73, the four length entries of the search box
 
 
 def fl(s, n=None):
@@ -134,6 +137,14 @@ def main():
     }
     json.dump(out, open(OUT, "w"), indent=1)
     print("wrote", OUT, {k: (len(v["bodies"]), len(v["joints"]), len(v["geoms"]), len(v["motors"]), len(v["pairs"])) for k, v in out.items()})
+    # walker2d over its length box: both corners and three seeded interior points (3 decimals, so a test xi can state them exactly)
+    lo, hi = WALKER_LENGTH_BOX
+    sizes = [[lo] * 4, [hi] * 4] + [[round(float(x), 3) for x in row] for row in np.random.RandomState(2021).uniform(lo, hi, (3, 4))]
+    more = {}
+    for k, size in enumerate(sizes):
+        more["walker2d_size_%d" % k] = dict(parse(render("walker2d.xml", size), "walker2d_size_%d" % k), size=size)
+    json.dump(more, open(OUT_SIZES, "w"), indent=1)
+    print("wrote", OUT_SIZES, {k: v["size"] for k, v in more.items()})
 
 
 if __name__ == "__main__":

@@ -1,6 +1,9 @@
-"""Self-consistency of the fp64 physics oracle (oracle/mjo_core.c).  True mujoco-py parity is
-UNPINNED (MuJoCo absent, reference has no numeric tests) -- these tests pin what can be pinned:
-recalled public model constants, conservation laws and force balance."""
+"""Self-consistency of the fp64 physics oracle (oracle/mjo_core.c): recalled public model constants, conservation laws and force
+balance.  What the oracle computes for the SMOOTH dynamics -- body masses, COMs and inertia tensors, M(q), the bias, passive and
+actuator forces, unconstrained integration, the humanoid's cinert / cvel -- is pinned independently of its author by
+tests/test_first_principles_host.py (a numpy restatement of rigid-body mechanics from the rendered MJCF tables).  What stays pinned
+to the oracle alone, MuJoCo being absent and the reference holding no numeric tests: collision, the constraint rows and the solvers,
+and the 2.1.0 compiler's split of a capsule's mass between cylinder and caps."""
 import numpy as np
 import pytest
 
@@ -29,13 +32,22 @@ def test_model_dimensions():
     assert list(oracle_constants("hopper")["qpos0"]) == [0, 1.25, 0, 0, 0, 0]
 
 
-@pytest.mark.parametrize("kind,nq,tol", [("hopper", 6, 1e-11), ("walker2d", 9, 1e-9), ("halfcheetah", 9, 1e-3)])
+# the humanoid's row: airborne and spinning (random root orientation, root spin and joint rates up to 2 rad/s); measured drift over 100
+# steps 3.8e-8, 4.1e-8 and 7.0e-7 relative (joint springs kept).  Its root quaternion is advanced by the weighted sum of the RK4 stage
+# rotation vectors (mj_RungeKutta), which is second order in the step for a body whose spin axis moves.  tests/test_humanoid_host.py holds the same drift to 1e-6 at
+# rates up to 1 rad/s; a second-order term grows with the square of the rates, so at 2 rad/s the bound is 4e-6, rounded up to 5e-6.
+@pytest.mark.parametrize("kind,nq,tol", [("hopper", 6, 1e-11), ("walker2d", 9, 1e-9), ("halfcheetah", 9, 1e-3), ("humanoid", 24, 5e-6)])
 def test_energy_conservation(kind, nq, tol):
     """M(q) and c(q,v) are consistent: a conservative copy of the model keeps KE+PE under RK4."""
     rng = np.random.RandomState(0)
     for _ in range(3):
-        q = rng.uniform(-.5, .5, nq); q[1] += 3; v = rng.uniform(-2, 2, nq)
+        if kind == "humanoid":
+            q = np.array([0, 0, 3.0, 1, 0, 0, 0] + [0] * 17, dtype=float); q[7:] += rng.uniform(-.5, .5, 17)
+            qq = rng.randn(4); q[3:7] = qq / np.linalg.norm(qq); v = rng.uniform(-2, 2, 23)
+        else:
+            q = rng.uniform(-.5, .5, nq); q[1] += 3; v = rng.uniform(-2, 2, nq)
         e0, e1 = oracle_energy_drift(kind, 100, q, v)
+        print("%s: relative energy drift over 100 steps %.1e" % (kind, (e1 - e0) / abs(e0)))
         assert abs(e1 - e0) <= tol * abs(e0)
     if kind == "halfcheetah":   # the residual there is RK4 truncation on the stiff joint springs
         e0, e1 = oracle_energy_drift(kind, 100, q, v, keep_springs=False)
