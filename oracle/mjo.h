@@ -175,6 +175,15 @@ int mjo_model_constants(int kind, const double* size, double* body_mass, double*
                         double* body_ipos, double* body_invweight0, double* dof_invweight0,
                         double* qpos0, int* dims);
 
+/* contact list of one state: rows of 10 = (geom1, geom2, dist, pos x,y,z, normal x,y,z, dim); returns the number written */
+int mjo_probe_contacts(int kind, const double* qpos, const double* qvel, const double* xi, double* out, int max_rows);
+/* constraint rows of one state: efc_* row by row (J packed [nefc][nv]), qacc, qacc_smooth, qM, meaninertia, solver_iter; any
+ * output may be NULL.  Returns nefc (-2: more than max_rows rows). */
+int mjo_probe_rows(int kind, const double* qpos, const double* qvel, const double* action, const double* xi, int max_rows,
+                   double* efc_J, double* efc_pos, double* efc_margin, double* efc_diagApprox, double* efc_R, double* efc_aref,
+                   int* efc_type, double* efc_force, double* qacc, double* qacc_smooth, double* qM, double* meaninertia,
+                   int* solver_iter);
+
 /* parity tests tighten the Newton tolerance (default: the model's 1e-8) */
 void mjo_set_tolerance(double tol);
 

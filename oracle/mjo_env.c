@@ -415,3 +415,41 @@ int mjo_model_dump(int kind, const double* size, double* jnt, double* geom, doub
   free(m); free(d);
   return 0;
 }
+
+/* constraint rows of one state (tests): everything mj_forward leaves in efc_*, row by row, plus qacc, qacc_smooth, qM, the model's
+ * meaninertia and the solver's iteration count.  J is [nefc][nv] packed; any output may be NULL.  Returns nefc (-1: bad kind,
+ * -2: more than max_rows rows). */
+int mjo_probe_rows(int kind, const double* qpos, const double* qvel, const double* action, const double* xi, int max_rows,
+                   double* efc_J, double* efc_pos, double* efc_margin, double* efc_diagApprox, double* efc_R, double* efc_aref,
+                   int* efc_type, double* efc_force, double* qacc, double* qacc_smooth, double* qM, double* meaninertia,
+                   int* solver_iter) {
+  mjoEnv* e = (mjoEnv*)malloc(sizeof(mjoEnv));
+  if (mjo_env_init(e, kind, 0)) { free(e); return -1; }
+  if (xi) mjo_env_set_task(e, xi);
+  mjo_env_set_state(e, qpos, qvel);
+  int nv = e->model.nv;
+  for (int u = 0; u < e->model.nu; u++) e->data.ctrl[u] = action ? action[u] : 0;
+  if (g_tolerance > 0) e->model.tolerance = g_tolerance;
+  mjo_forward(&e->model, &e->data);
+  const mjoData* d = &e->data; int ne = d->nefc;
+  if (ne > max_rows) { free(e); return -2; }
+  for (int r = 0; r < ne; r++) {
+    if (efc_J) for (int k = 0; k < nv; k++) efc_J[r * nv + k] = d->efc_J[r * MJO_MAXV + k];
+    if (efc_pos) efc_pos[r] = d->efc_pos[r];
+    if (efc_margin) efc_margin[r] = d->efc_margin[r];
+    if (efc_diagApprox) efc_diagApprox[r] = d->efc_diagApprox[r];
+    if (efc_R) efc_R[r] = d->efc_R[r];
+    if (efc_aref) efc_aref[r] = d->efc_aref[r];
+    if (efc_type) efc_type[r] = d->efc_type[r];
+    if (efc_force) efc_force[r] = d->efc_force[r];
+  }
+  for (int i = 0; i < nv; i++) {
+    if (qacc) qacc[i] = d->qacc[i];
+    if (qacc_smooth) qacc_smooth[i] = d->qacc_smooth[i];
+    if (qM) for (int k = 0; k < nv; k++) qM[i * nv + k] = d->qM[i * MJO_MAXV + k];
+  }
+  if (meaninertia) *meaninertia = e->model.meaninertia;
+  if (solver_iter) *solver_iter = d->solver_iter;
+  free(e);
+  return ne;
+}

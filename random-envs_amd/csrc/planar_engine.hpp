@@ -375,7 +375,7 @@ REX_HD void capsule_capsule_2d(const T (&p1)[2], const T (&a1)[2], T l1, T r1, c
     T len = sqrt_t(dx * dx + dz * dz), d = len - r1 - r2;
     if (d > margin) return;
     T ux = T(1), uz = T(0);
-    if (len >= T(1e-15)) { const T il = rcp_t(len); ux = dx * il; uz = dz * il; }
+    if (len >= T(1e-15)) { const T il = rcp_t(len); ux = dx * il; uz = dz * il; }   // coincident centres: normal (1, 0) ([3P] len < mjMINVAL)
     T px_ = c1x + ux * (r1 + d * T(0.5)), pz_ = c1z + uz * (r1 + d * T(0.5));
     // value selects, not `if (!H.h0) H.d0 = d; else H.d1 = d;`: LLVM sinks the two stores into one store through a selected
     // ADDRESS, which puts H into scratch (a store + a load with its own wait per field and evaluation)
@@ -390,10 +390,15 @@ REX_HD void capsule_capsule_2d(const T (&p1)[2], const T (&a1)[2], T l1, T r1, c
   if (abs_t(det) >= T(1e-15)) {
     const T idet = rcp_t(det), imc = rcp_t(mc), ima = rcp_t(ma);
     T x1 = (mc * u - mb * v) * idet, x2 = (ma * v - mb * u) * idet;
+    // Non-parallel axes in ONE plane: a stationary point inside both segments is where they CROSS, so the closest points are one point
+    // (d = -(r1 + r2), normal (1, 0) by the rule above).  Said outright: computed, the two points come out eps / |det| apart -- below
+    // 1e-15 in fp64 at most angles, never in fp32 -- and their difference is rounding, not a direction.
+    const bool cross = x1 <= l1 && x1 >= -l1 && x2 <= l2 && x2 >= -l2;
     if (x1 > l1) { x1 = l1; x2 = (v - mb * l1) * imc; } else if (x1 < -l1) { x1 = -l1; x2 = (v + mb * l1) * imc; }
     if (x2 > l2) { x2 = l2; x1 = (u - mb * l2) * ima; } else if (x2 < -l2) { x2 = -l2; x1 = (u + mb * l2) * ima; }
     if (x1 > l1) x1 = l1; else if (x1 < -l1) x1 = -l1;
-    sphere(p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p2[0] + a2[0] * x2, p2[1] + a2[1] * x2);
+    const T c1x = p1[0] + a1[0] * x1, c1z = p1[1] + a1[1] * x1;
+    sphere(c1x, c1z, cross ? c1x : p2[0] + a2[0] * x2, cross ? c1z : p2[1] + a2[1] * x2);
     return;
   }
   // parallel axes: end points of segment 1 against segment 2, then of 2 against 1; first two hits

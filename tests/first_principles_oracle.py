@@ -137,9 +137,10 @@ def _mv(R, x):
 class Model:
     """One kinematic tree from a rendered table: everything in world coordinates at qpos0."""
 
-    def __init__(self, key, capsule_volume="mujoco210", flaw=None):
+    def __init__(self, key, capsule_volume="mujoco210", flaw=None, table=None):
+        """table: the rendered table itself, for a caller that holds one which is not in tables() (key is then only its name)"""
         assert flaw is None or flaw in FLAWS, flaw
-        t = tables()[key]
+        t = tables()[key] if table is None else table
         self.key, self.flaw, self.t = key, flaw, t
         self.names = [b["name"] for b in t["bodies"]]
         self.nb = len(self.names)

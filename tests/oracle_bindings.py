@@ -13,6 +13,7 @@ DIMS = {"humanoid": dict(nq=24, nv=23, nu=17, nx=30, nobs=376, frame_skip=5),
         "hopper": dict(nq=6, nv=6, nu=3, nx=4, nobs=11, frame_skip=4),
         "walker2d": dict(nq=9, nv=9, nu=6, nx=13, nobs=17, frame_skip=4),
         "halfcheetah": dict(nq=9, nv=9, nu=6, nx=8, nobs=17, frame_skip=5)}
+MAXCON, MAXEFC = 96, 320      # MJO_MAXCON, MJO_MAXEFC of oracle/mjo.h
 _D = ctypes.POINTER(ctypes.c_double)
 _lib = None
 
@@ -105,9 +106,31 @@ def oracle_contacts(kind, qpos, qvel, xi):
     """rows: geom1, geom2, dist, pos(3), normal(3), dim"""
     L = lib()
     q = np.ascontiguousarray(qpos, dtype=np.float64); v = np.ascontiguousarray(qvel, dtype=np.float64)
-    x = np.ascontiguousarray(xi, dtype=np.float64); out = np.zeros(10 * 32)
-    n = L.mjo_probe_contacts(KINDS[kind], _p(q), _p(v), _p(x), _p(out), 32)
-    return out.reshape(32, 10)[:n].copy()
+    x = np.ascontiguousarray(xi, dtype=np.float64); out = np.zeros(10 * MAXCON)
+    n = L.mjo_probe_contacts(KINDS[kind], _p(q), _p(v), _p(x), _p(out), MAXCON)
+    return out.reshape(MAXCON, 10)[:n].copy()
+
+
+def oracle_rows(kind, qpos, qvel, action, xi, tolerance=1e-12):
+    """Constraint rows of one state as mj_forward leaves them: efc_J [ne, nv], efc_pos, efc_margin, efc_diagApprox, efc_R, efc_aref,
+    efc_type (0 limit, 1 frictionless contact, 2 pyramid edge), efc_force, qacc, qacc_smooth, qM, meaninertia, solver_iter and the
+    contact list (rows: geom1, geom2, dist, pos(3), normal(3), dim)."""
+    d = DIMS[kind]; L = lib(); L.mjo_set_tolerance(tolerance)
+    nv = d["nv"]
+    q = np.ascontiguousarray(qpos, dtype=np.float64); v = np.ascontiguousarray(qvel, dtype=np.float64)
+    a = np.ascontiguousarray(action, dtype=np.float64); x = np.ascontiguousarray(xi, dtype=np.float64)
+    J = np.zeros(MAXEFC * nv); r = {k: np.zeros(MAXEFC) for k in ("efc_pos", "efc_margin", "efc_diagApprox", "efc_R", "efc_aref", "efc_force")}
+    ty = np.zeros(MAXEFC, dtype=np.int32); qacc = np.zeros(nv); qs = np.zeros(nv); M = np.zeros((nv, nv))
+    mi, it = ctypes.c_double(), ctypes.c_int()
+    I = ctypes.POINTER(ctypes.c_int)
+    ne = L.mjo_probe_rows(KINDS[kind], _p(q), _p(v), _p(a), _p(x), MAXEFC, _p(J), _p(r["efc_pos"]), _p(r["efc_margin"]),
+                          _p(r["efc_diagApprox"]), _p(r["efc_R"]), _p(r["efc_aref"]), ty.ctypes.data_as(I), _p(r["efc_force"]),
+                          _p(qacc), _p(qs), _p(M), ctypes.byref(mi), ctypes.byref(it))
+    assert ne >= 0, ne
+    out = {k: x_[:ne].copy() for k, x_ in r.items()}
+    out.update(efc_J=J[:ne * nv].reshape(ne, nv).copy(), efc_type=ty[:ne].copy(), qacc=qacc, qacc_smooth=qs, qM=M,
+               meaninertia=mi.value, solver_iter=it.value, nefc=ne, contacts=oracle_contacts(kind, qpos, qvel, xi))
+    return out
 
 
 def oracle_humanoid_step(qpos, qvel, action, xi, xipos_x_prev=None, nthreads=8):

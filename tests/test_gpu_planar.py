@@ -120,8 +120,10 @@ def test_every_solver_configuration_matches_the_oracle(torch_mod, kind, knobs):
 def test_hopper_contact_rich_and_limit_states(torch_mod, shape):
     """random (not rollout) states: deeper penetrations, joint limits violated, large velocities -- practically every wave leaves the
     feet-only path, so this is the test of the general solver in its three forms: the LIST solver of the two-lanes-per-env kernels (the default up
-    to 32 768 envs: floor units and capsule-capsule rows in the LDS column, two-group correction), the unrolled per-slot one of the
-    one-lane-per-env kernels, and the rolled row-list one of the two-waves-per-SIMD kernel"""
+    to 32 768 envs: floor units in the LDS column, two-group correction), the unrolled per-slot one of the
+    one-lane-per-env kernels, and the rolled row-list one of the two-waves-per-SIMD kernel.  These states reach NO capsule-capsule
+    contact (with this generator only the floor pairs of the leg and the foot occur): the capsule-capsule rows are tested on the device
+    by the folded-leg sample of tests/test_gpu_contact_reference.py"""
     rolled = 1 if shape == "rolled" else 0
     import random_envs_amd as rex
     from parity_util import create_knobs
