@@ -108,7 +108,7 @@ __device__ __attribute__((noinline)) void walker_derive_call(const DevState& s, 
 // PAIR: two lanes per environment (lane 2i and 2i + 1 both hold env i; planar_spec.hpp "two lanes per environment"):
 // the launch has 2 B lanes in 64-lane blocks = 32 envs per wave, exactly the envs-per-wave of the 32-lane 1-lane-per-env
 // launch, but the wave is full and the per-slot work of the feet-only solver is split over the two lanes.
-// ROLLED: the general solver instantiation as runtime loops over a row list in scratch (planar_engine.hpp::solve_newton_rolled): the kernel
+// ROLLED: the general solver instantiation as runtime loops over a row list in scratch (planar_newton_rolled.hpp::solve_newton_rolled): the kernel
 // then fits 256 registers and is built for TWO waves per SIMD -- hopper handles with more full one-lane-per-env waves than the GPU has SIMDs (rex_create).
 template <class S, bool PAIR, bool ROLLED = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLLED ? 2 : REX_STEP_WAVES, ROLLED ? 2 : REX_STEP_WAVES)))

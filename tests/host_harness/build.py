@@ -58,7 +58,7 @@ def set_fast(flag):
 
 
 def set_rolled(flag):
-    """1 = the general path as the rolled row-list solver (planar_engine.hpp::solve_newton_rolled: what the 256-register hopper kernel of
+    """1 = the general path as the rolled row-list solver (planar_newton_rolled.hpp::solve_newton_rolled: what the 256-register hopper kernel of
     handles with >= 65 536 envs runs), 0 = the unrolled per-slot instantiation"""
     lib().ph_set_rolled(int(flag))
 

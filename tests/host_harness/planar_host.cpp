@@ -15,7 +15,7 @@ extern "C" void ph_set_ls(int ls_max, int ls_free) { g_ls_max = ls_max; g_ls_fre
 static int g_last_mode = -1;   // SolveStats::mode of the last ph_forward
 extern "C" void ph_set_fast(int f) { g_fast = f; }
 static int g_rolled = 0;   // the GEN flag of forward(): 0 = unrolled general instantiations, 1 = the rolled ROW-list solver (the 256-register hopper kernel,
-                           // planar_engine.hpp::solve_newton_rolled), 2 = the LIST solver of the two-lanes-per-env kernels (solve_newton_list; one lane walks both ends here)
+                           // planar_newton_rolled.hpp::solve_newton_rolled), 2 = the LIST solver of the two-lanes-per-env kernels (solve_newton_list; one lane walks both ends here)
 extern "C" void ph_set_rolled(int r) { g_rolled = r; }
 extern "C" int ph_last_mode() { return g_last_mode; }
 

@@ -43,7 +43,7 @@ walker2d 8.3e-9, 7.2e-11 / 1.4e-9), still 100x under the weakest flaw.
 WHAT FAILED, and was fixed: the fp32 planar engine on the folded hopper.  Where two capsule axes CROSS in the plane the two closest
 points coincide, and MuJoCo's rule gives the normal (1, 0, 0) when their distance is below 1e-15.  In fp64 the crossing point comes out
 1e-17 apart; in fp32 1e-8 apart, so the engine normalised rounding noise: 31 of the first 128 folded states missed the 5e-4 gate with
-|dqvel|rel up to 1.4 in every solver form, none explained by the oracle's conditioning.  planar_engine.hpp::capsule_capsule_2d now
+|dqvel|rel up to 1.4 in every solver form, none explained by the oracle's conditioning.  planar_contacts.hpp::capsule_capsule_2d now
 says it geometrically: non-parallel axes in one plane whose stationary point lies inside both segments CROSS there, and the two
 closest points are taken as one point (no threshold, no dependence on the crossing angle).  With it the worst folded lane is 3.3e-7 /
 3.9e-6 and no lane of any sample needs the explained clause.

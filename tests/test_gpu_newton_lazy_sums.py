@@ -1,4 +1,4 @@
-"""The Newton solvers' lazily computed line-search sums (planar_engine.hpp: solve_newton / solve_newton_list, LAZY) on the device.
+"""The Newton solvers' lazily computed line-search sums (planar_newton.hpp: solve_newton, planar_newton_list.hpp: solve_newton_list; LAZY) on the device.
 
 An iteration that does not search skips M sr, phi'(0), the curvature and the phi' / phi'' sums, and carries Ma only where a further
 iteration reads it; which of the two forms an iteration takes is a wave-uniform scalar branch on (iteration, ls_free, ls_max), and the

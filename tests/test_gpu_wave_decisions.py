@@ -1,4 +1,4 @@
-"""The wave-uniform decisions of forward() and of the Newton solvers (planar_engine.hpp) on the device, with waves whose lanes disagree.
+"""The wave-uniform decisions of forward() (planar_engine.hpp) and of the Newton solvers (planar_newton.hpp, planar_newton_list.hpp) on the device, with waves whose lanes disagree.
 
 Host builds have one-lane "waves" (REX_WAVE_ANY(x) is x), so only the device can get a ballot wrong: which solver instantiation a wave
 enters (forward(): none, feet-only, general, general + self rows), the one exit test at the end of a Newton pass (does any lane iterate on,

@@ -1,4 +1,4 @@
-"""The Newton solvers compute the line-search sums and the carry of Ma only on the paths that read them (planar_engine.hpp, LAZY):
+"""The Newton solvers compute the line-search sums and the carry of Ma only on the paths that read them (planar_newton.hpp, planar_newton_list.hpp: LAZY):
 the same operations on the same values, so the fp32 host build must reproduce, word for word, what the eager code gave.
 
 tests/golden/planar_fp32_bits.npz was recorded from the eager solvers (tests/golden/record_planar_bits.py: seeded reset states,

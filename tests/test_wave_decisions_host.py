@@ -1,4 +1,4 @@
-"""The wave-uniform decisions of the Newton solvers (planar_engine.hpp: solve_newton, solve_newton_list, CorrPlan, corr_step) were thinned out:
+"""The wave-uniform decisions of the Newton solvers (planar_newton.hpp: solve_newton, planar_newton_list.hpp: solve_newton_list, planar_newton_common.hpp: CorrPlan, corr_step) were thinned out:
 the correction plan is formed without short circuits and early returns, both ballots of the correction block are taken ahead of the one branch
 into it, the pair exchange of its pivot check no longer sits behind a divergent branch, and one place at the end of a pass decides whether
 the wave iterates on and only then brings Ma up to date (rebuilt after a correction trip -- the `ma_dirty` test at the top of every pass is
