@@ -21,7 +21,8 @@
  *     rex_step / rex_reset.
  *   - internal state is SoA [field][env]; I/O buffers are SoA too: obs is [obs_dim][batch],
  *     action is [act_dim][batch], xi is [task_dim][batch] (a torch [batch, dim] view is the
- *     zero-copy transpose).  reward is float[batch], done / truncated are uint8[batch].
+ *     zero-copy transpose).  reward is float[batch], done / truncated are uint8[batch].  The row-major calls (rex_step_rows,
+ *     rex_reset_rows) take action [batch][act_dim] and obs [batch][obs_dim] instead; everything else keeps its shape.
  *   - a handle is bound to one device; calls on one handle are not re-entrant.  Every entry point that enqueues work, copies or
  *     synchronises makes the handle's device the calling thread's current device first, so one thread may drive one handle per GPU.
  *   - environment: REX_LANES / REX_PAIR / REX_ROLLED / REX_HUM_PAIR / REX_HUM_FUSED_RESET / REX_FUSED_DERIVE (launch shape) and
@@ -122,6 +123,30 @@ int rex_reset(rex_t* h, const uint8_t* mask, float* obs_out, void* stream);
  * (observation before auto-reset). */
 int rex_step(rex_t* h, const void* action, float* obs_out, float* reward_out, uint8_t* done_out,
              uint8_t* truncated_out, float* terminal_obs_out, void* stream);
+
+/* Row-major calls: the reference's own loop, `obs, reward, done, info = env.step(action)` over action[batch, act_dim] and
+ * obs[batch, obs_dim] (test_random_policy.py:25-32, random_hopper.py:83-98), with nothing between the caller's buffers and the kernels: the
+ * planar chains' and the cart-pole's step and reset kernels read and write the rows themselves (a compile-time layout of the same kernels, so
+ * the state, the counters and every value are those of rex_step / rex_reset, bit for bit), and either layout may be used on a handle at any
+ * time.  reward, done, truncated and the info buffer keep their [batch] and [n_info][batch] shapes.
+ *
+ * rex_rows_enable allocates what the handle's kind needs for these calls and is idempotent; rex_destroy frees it.  Only the humanoid needs
+ * anything: its kernels keep their SoA buffers, so its row-major calls run them into staging of the handle -- action [17][batch], obs and
+ * terminal obs [376][batch] each, 769 floats per env, roughly 100 MB at 32 768 envs -- between an action kernel and a tiled transposer (three
+ * launches beside a 1.9 ms step; the reset launch as well where the auto-reset is not fused).  Elsewhere it is a no-op and optional.  The
+ * call allocates (and so synchronises the device). */
+int rex_rows_enable(rex_t* h);
+/* MujocoEnv.reset + reset_model (jinja_mujoco_env.py:141-144, random_hopper.py:112-120) as rex_reset does it, the observation of the
+ * masked lanes (all lanes if mask==NULL) written to obs_rows [dev, batch*obs_dim, row-major; required].  Rows of unmasked envs are not
+ * written.  CartPole: obs_rows 16-byte aligned (one store per row). */
+int rex_reset_rows(rex_t* h, const uint8_t* mask, float* obs_rows /*[B, obs_dim]*/, void* stream);
+/* step() (random_hopper.py:83-98; the loop of test_random_policy.py:25-32) as rex_step does it -- same state transitions, counters, timing
+ * bracket and auto-reset -- with action_rows [dev]: float[batch*act_dim] row-major (CartPole: int32[batch]), obs_rows and terminal_obs_rows
+ * [dev, batch*obs_dim, row-major].  done_out / truncated_out bytes are 0 or 1 (a caller may allocate them as bool).  terminal_obs_rows
+ * (NULL to skip, like truncated_out) is DEFINED ON THE ROWS WHOSE done IS SET; the other rows are left as they were.  REX_ERR_ARG for a null required buffer (or a misaligned CartPole row buffer),
+ * REX_ERR_STATE for a humanoid handle without rex_rows_enable; neither launches anything. */
+int rex_step_rows(rex_t* h, const void* action_rows, float* obs_rows, float* reward_out, uint8_t* done_out,
+                  uint8_t* truncated_out /*nullable*/, float* terminal_obs_rows /*nullable*/, void* stream);
 
 /* Offline replay of logged transitions under candidate xi (get_full_mjstate + set_sim_state + step: random_hopper.py:128-152,
  * random_half_cheetah.py:136-158, random_walker2d.py:161-185, random_humanoid.py:244-270, and the Unmodeled task files'

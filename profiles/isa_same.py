@@ -5,7 +5,7 @@
 
 A function is the text from its label up to its `.Lfunc_end`: the instructions and, for a kernel, the
 `.amdhsa_kernel ... .end_amdhsa_kernel` descriptor.  Local labels carry the function's position in the file
-(`.LBB12_3`); the position is dropped, so functions that only moved compare equal.  Exit status 0: same set of
+(`.LBB12_3`, and `BB12_3` in the compiler's loop comments); the position is dropped, so functions that only moved compare equal.  Exit status 0: same set of
 functions, every one identical.
 """
 import re
@@ -14,6 +14,7 @@ import sys
 BEGIN = re.compile(r"^([A-Za-z_$][\w$.]*):\s*; @")
 END = re.compile(r"^\.Lfunc_end\d+:")
 LOCAL = re.compile(r"\.L([A-Za-z_]+)\d+_(\d+)")
+BLOCK_REF = re.compile(r"\bBB\d+_(\d+)")     # the same position in the compiler's comments ("in Loop: Header=BB12_3", "Child Loop BB12_7")
 
 
 def functions(path):
@@ -28,7 +29,7 @@ def functions(path):
                 out[name] = body
                 name = None
             else:
-                body.append(LOCAL.sub(r".L\1_\2", line.rstrip()))
+                body.append(BLOCK_REF.sub(r"BB_\1", LOCAL.sub(r".L\1_\2", line.rstrip())))
     return out
 
 

@@ -27,6 +27,7 @@ SYMBOLS = [
     "rex_per_read_counters",
     "rex_rbuf_gather_nstep", "rex_rbuf_sample_nstep", "rex_per_sample_nstep",
     "rex_rbuf_gather_seq", "rex_rbuf_sample_seq", "rex_per_sample_seq",
+    "rex_rows_enable", "rex_reset_rows", "rex_step_rows",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -92,6 +93,9 @@ def lib():
     L.rex_seed.argtypes = [vp, u64]
     L.rex_reset.argtypes = [vp, vp, vp, vp]
     L.rex_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rex_rows_enable.argtypes = [vp]
+    L.rex_reset_rows.argtypes = [vp, vp, vp, vp]
+    L.rex_step_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_get_state.argtypes = [vp, vp, vp, vp]
     L.rex_set_state.argtypes = [vp, vp, vp, vp]
     L.rex_get_task.argtypes = [vp, vp, vp]

@@ -5,6 +5,9 @@
 // ------------------------------------------------------------------------------------------
 // CartPole (random_envs/random_cartpole.py:172-229).  qpos = (x, theta), qvel = (x_dot, theta_dot).
 // ------------------------------------------------------------------------------------------
+// ROWS: action stays int32[B]; obs and term_obs are row-major [B][4], one 16-byte store per env (rex_step_rows / rex_reset_rows; the buffers are
+// 16-byte aligned, which the entry points check)
+template <bool ROWS = false>
 __global__ void __launch_bounds__(64) cartpole_step_kernel(DevState s, StepFlags fl, const int* __restrict__ action,
                                                            float* __restrict__ obs, float* __restrict__ reward,
                                                            unsigned char* __restrict__ done_out, unsigned char* __restrict__ trunc_out,
@@ -32,13 +35,19 @@ __global__ void __launch_bounds__(64) cartpole_step_kernel(DevState s, StepFlags
   bool trunc = fl.time_limit && t >= fl.max_steps && !dn;
   bool d = dn || trunc;
   s.done[i] = (unsigned char)((dn || was_done) ? 1 : 0) | (unsigned char)(d ? 2 : 0);
-  obs[i] = x; obs[B + i] = xd; obs[2 * B + i] = th; obs[3 * B + i] = thd;   // np.array(self.state) :224
-  if (term_obs) { term_obs[i] = x; term_obs[B + i] = xd; term_obs[2 * B + i] = th; term_obs[3 * B + i] = thd; }
+  if constexpr (ROWS) {
+    reinterpret_cast<float4*>(obs)[i] = make_float4(x, xd, th, thd);
+    if (term_obs && d) reinterpret_cast<float4*>(term_obs)[i] = make_float4(x, xd, th, thd);   // (defined on the done rows only, rex.h)
+  } else {
+    obs[i] = x; obs[B + i] = xd; obs[2 * B + i] = th; obs[3 * B + i] = thd;   // np.array(self.state) :224
+    if (term_obs) { term_obs[i] = x; term_obs[B + i] = xd; term_obs[2 * B + i] = th; term_obs[3 * B + i] = thd; }
+  }
   reward[i] = r; done_out[i] = d ? 1 : 0;
   if (trunc_out) trunc_out[i] = trunc ? 1 : 0;
 }
 
 // reset(): state ~ U(-0.05, 0.05)^4 (random_cartpole.py:226-229). `resample` = set_random_task.
+template <bool ROWS = false>
 __global__ void __launch_bounds__(64) cartpole_reset_kernel(DevState s, DRParams dr, int resample, int reset_state,
                                                             const unsigned char* __restrict__ mask, int mask_bit,
                                                             float* __restrict__ obs) {
@@ -55,7 +64,10 @@ __global__ void __launch_bounds__(64) cartpole_reset_kernel(DevState s, DRParams
     for (int k = 0; k < 4; k++) v[k] = -0.05f + 0.1f * (1.0f - rocrand_uniform(&st));
     s.qpos[i] = v[0]; s.qvel[i] = v[1]; s.qpos[B + i] = v[2]; s.qvel[B + i] = v[3];
     s.t[i] = 0; s.done[i] = 0;
-    if (obs) { obs[i] = v[0]; obs[B + i] = v[1]; obs[2 * B + i] = v[2]; obs[3 * B + i] = v[3]; }
+    if (obs) {
+      if constexpr (ROWS) reinterpret_cast<float4*>(obs)[i] = make_float4(v[0], v[1], v[2], v[3]);
+      else { obs[i] = v[0]; obs[B + i] = v[1]; obs[2 * B + i] = v[2]; obs[3 * B + i] = v[3]; }
+    }
   }
   if (resample && dr.type != REX_DR_NONE) {
     sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, i, s.counters);

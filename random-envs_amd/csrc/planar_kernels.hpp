@@ -37,7 +37,9 @@ __device__ __forceinline__ void pin_uniform(PlanarGeom<float, S>& G) {
 
 // observation: concat(qpos[1:], qvel) (random_hopper.py:100-110, random_half_cheetah.py:112-121,
 // random_walker2d.py:133-142) + optional N(0, noise_var)
-template <class S>
+// ROWS (here and in every kernel below): the caller's buffer is row-major [B][NOBS] / [B][NU] (the gym surface, rex_step_rows / rex_reset_rows)
+// instead of the SoA [NOBS][B] / [NU][B] of rex_step; a compile-time choice, so the SoA instantiations keep their code
+template <class S, bool ROWS = false>
 __device__ __forceinline__ void write_obs(const float (&q)[S::NV], const float (&v)[S::NV], float* __restrict__ obs,
                                           long long B, unsigned i, bool noisy, float noise_std,
                                           rocrand_state_philox4x32_10* st) {
@@ -45,7 +47,8 @@ __device__ __forceinline__ void write_obs(const float (&q)[S::NV], const float (
     constexpr int k = KK;
     float o = k < S::NV - 1 ? q[k + 1] : v[k - (S::NV - 1)];
     if (noisy) o += noise_std * rocrand_normal(st);
-    (obs + (size_t)k * B)[i] = o;
+    if constexpr (ROWS) obs[(size_t)i * S::NOBS + k] = o;
+    else (obs + (size_t)k * B)[i] = o;
   });
 }
 
@@ -88,7 +91,7 @@ __device__ __forceinline__ void reset_state_values(unsigned long long seed, unsi
   }
 }
 
-template <class S>
+template <class S, bool ROWS = false>
 __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepFlags& fl, const DRParams& dr, int resample,
                                                   int reset_state, unsigned i, float* __restrict__ obs);
 // walker2d: the per-env model constants of lane i from its xi lengths (what build_model() does inside
@@ -110,7 +113,9 @@ __device__ __attribute__((noinline)) void walker_derive_call(const DevState& s, 
 // launch, but the wave is full and the per-slot work of the feet-only solver is split over the two lanes.
 // ROLLED: the general solver instantiation as runtime loops over a row list in scratch (planar_newton_rolled.hpp::solve_newton_rolled): the kernel
 // then fits 256 registers and is built for TWO waves per SIMD -- hopper handles with more full one-lane-per-env waves than the GPU has SIMDs (rex_create).
-template <class S, bool PAIR, bool ROLLED = false>
+// ROWS: action is [B][NU], obs and term_obs are [B][NOBS] (one env's row is 44 - 68 contiguous bytes and the rows of a wave's envs one contiguous
+// block); NU and NOBS are compile-time, so the argument segment is the SoA kernel's and everything between the loads and the tail is the same code.
+template <class S, bool PAIR, bool ROLLED = false, bool ROWS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLLED ? 2 : REX_STEP_WAVES, ROLLED ? 2 : REX_STEP_WAVES)))
 planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
                                                          SolParams<float> sp, const float* __restrict__ action,
@@ -136,7 +141,9 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
   const int t_in = s.t[i]; const unsigned ep_in = s.episode[i];
   float q[S::NV], v[S::NV], ctrl[S::NU], xi[S::NXI];
   static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; q[k] = (s.qpos + (size_t)k * B)[i]; v[k] = (s.qvel + (size_t)k * B)[i]; });
-  static_for<0, S::NU>([&](auto KK) { constexpr int k = KK; ctrl[k] = (action + (size_t)k * B)[i]; });
+  static_for<0, S::NU>([&](auto KK) { constexpr int k = KK;
+    if constexpr (ROWS) ctrl[k] = action[(size_t)i * S::NU + k];
+    else ctrl[k] = (action + (size_t)k * B)[i]; });
   static_for<0, S::NXI>([&](auto KK) { constexpr int k = KK; xi[k] = (s.xi + (size_t)k * B)[i]; });
   tail_park[threadIdx.x] = (unsigned)t_in; tail_park[64 + threadIdx.x] = ep_in;
   PlanarGeom<float, S> G; load_geom<S>(s, i, ugeom, G);
@@ -205,7 +212,10 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
   obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq,
                 (unsigned long long)ep_prev * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE);
   // what always carries the STEPPED values goes out first
-  if (term_obs) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (term_obs + (size_t)k * B)[io] = ob[k]; });
+  // (row-major: the terminal observation is defined on the done rows and only those are written, rex.h)
+  if (term_obs && (!ROWS || d)) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK;
+    if constexpr (ROWS) term_obs[(size_t)io * S::NOBS + k] = ob[k];
+    else (term_obs + (size_t)k * B)[io] = ob[k]; });
   reward[io] = r; done_out[io] = d ? 1 : 0;
   if (trunc_out) trunc_out[io] = trunc ? 1 : 0;
   if (fl.info) { fl.info[io] = dx / dt; (fl.info + (size_t)B)[io] = -S::CTRL_COST * asq; }   // info: reward_run, reward_ctrl (random_half_cheetah.py:105-110)
@@ -242,13 +252,15 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
     static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; (s.qpos + (size_t)k * B)[io] = q[k]; (s.qvel + (size_t)k * B)[io] = v[k]; });
     s.done[io] = dflag;
   }
-  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK; (obs + (size_t)k * B)[io] = ob[k]; });
+  static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK;
+    if constexpr (ROWS) obs[(size_t)io * S::NOBS + k] = ob[k];
+    else (obs + (size_t)k * B)[io] = ob[k]; });
   REX_WSTEP_EXIT(tp0, tw0, tk0, tk1, tt0, tr0);
 }
 
 // reset_model (random_hopper.py:112-120, random_half_cheetah.py:123-131, random_walker2d.py:144-153)
 // + set_random_task (random_env.py:37-39) for one lane.
-template <class S>
+template <class S, bool ROWS>
 __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepFlags& fl, const DRParams& dr, int resample,
                                                   int reset_state, unsigned i, float* __restrict__ obs) {
   const long long B = s.B;
@@ -269,7 +281,7 @@ __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepF
     if (obs) {
       rocrand_state_philox4x32_10 st2;
       if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
-      write_obs<S>(q, v, obs, B, i, fl.noisy != 0, fl.noise_std, &st2);
+      write_obs<S, ROWS>(q, v, obs, B, i, fl.noisy != 0, fl.noise_std, &st2);
     }
   }
   if (resample && dr.type != REX_DR_NONE) {
@@ -281,14 +293,14 @@ __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepF
 // pending_bit: walker2d's auto-reset under DR -- the lane's geometry has to follow its NEW xi lengths, which is the derive
 // launch behind this one; the auto-reset mask is s.done itself and reset_lane clears it, so the reset leaves this bit for
 // walker_derive_kernel to find (and clear).
-template <class S>
+template <class S, bool ROWS = false>
 __global__ void __launch_bounds__(64) planar_reset_kernel(DevState s, StepFlags fl, DRParams dr, int resample, int reset_state,
                                                           const unsigned char* __restrict__ mask, int mask_bit,
                                                           float* __restrict__ obs, int pending_bit) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= s.B) return;
   if (mask && !(mask[i] & mask_bit)) return;
-  planar_reset_lane<S>(s, fl, dr, resample, reset_state, i, obs);
+  planar_reset_lane<S, ROWS>(s, fl, dr, resample, reset_state, i, obs);
   if (pending_bit) s.done[i] = (unsigned char)pending_bit;
 }
 

@@ -46,6 +46,7 @@
 #include "cartpole_kernels.hpp"
 #include "planar_kernels.hpp"
 #include "humanoid_kernels.hpp"
+#include "rows.hpp"
 
 using namespace rex;
 
@@ -145,6 +146,10 @@ struct rex_env {
   // rex_per_* (priority_replay.hpp): the two counters rex_per_enable allocates (invalid priorities, out-of-range update ids).  Priorities and
   // the sum tree belong to the caller.
   void* per_mem = nullptr;
+  // rex_step_rows / rex_reset_rows (rows.hpp): the humanoid's SoA staging rex_rows_enable allocates as one block -- action [act_dim][B], obs and
+  // terminal obs [obs_dim][B] each; the other kinds' kernels read and write the caller's rows themselves and have none
+  float* rows_mem = nullptr;
+  int rows_enabled = 0;
 };
 constexpr size_t EV_POOL = 8192;
 
@@ -328,6 +333,26 @@ static void launch_humanoid_step(HumanoidTag, rex_env* h, const DevState& dev, c
                        done_out, truncated_out, terminal_obs_out);
   }
 }
+// The humanoid's rows around its SoA kernels (rows.hpp; the staging block of rex_rows_enable: action, obs, terminal obs).
+static float* hum_rows_action(HumanoidTag, const rex_env* h) { return h->rows_mem; }
+static float* hum_rows_obs(HumanoidTag, const rex_env* h) { return h->rows_mem + (size_t)h->dims.act_dim * (size_t)h->B; }
+static float* hum_rows_term(HumanoidTag t, const rex_env* h) { return hum_rows_obs(t, h) + (size_t)h->dims.obs_dim * (size_t)h->B; }
+static int launch_rows_action(HumanoidTag t, rex_env* h, const float* action_rows, hipStream_t st) {
+  const long long n = (long long)h->dims.act_dim * h->B;
+  hipLaunchKernelGGL(rows::rows_action_kernel, dim3((unsigned)((n + rows::BLOCK - 1) / rows::BLOCK)), dim3(rows::BLOCK), 0, st, action_rows,
+                     hum_rows_action(t, h), h->dims.act_dim, (long long)h->B);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
+// obs staging -> obs_rows for the envs `keep` selects (all when null); terminal-obs staging -> term_rows (when given) for the envs with done_out set
+static int launch_rows_transpose(HumanoidTag t, rex_env* h, float* obs_rows, const uint8_t* keep, int keep_bit, float* term_rows, const uint8_t* done_out,
+                                 hipStream_t st) {
+  const dim3 grid((unsigned)rows::env_tiles(h->B), (unsigned)rows::dim_tiles(h->dims.obs_dim));
+  hipLaunchKernelGGL(rows::rows_transpose_kernel, grid, dim3(rows::BLOCK), 0, st, hum_rows_obs(t, h), obs_rows, keep, keep_bit, hum_rows_term(t, h), term_rows,
+                     done_out, h->dims.obs_dim, (long long)h->B);
+  HIP_TRY(hipGetLastError());
+  return REX_OK;
+}
 #endif
 
 // everything of rex_create that can fail after the handle exists: on any error the caller destroys the handle, which frees
@@ -464,6 +489,7 @@ extern "C" int rex_destroy(rex_t* h) {
   if (h->eplog_mem) hipFree(h->eplog_mem);
   if (h->rbuf_mem) hipFree(h->rbuf_mem);
   if (h->per_mem) hipFree(h->per_mem);
+  if (h->rows_mem) hipFree(h->rows_mem);
   for (auto e : h->ev0) hipEventDestroy(e);
   for (auto e : h->ev1) hipEventDestroy(e);
   delete h;
@@ -509,18 +535,21 @@ extern "C" int rex_set_autoreset(rex_t* h, int autoreset, int time_limit) {
 }
 extern "C" int rex_seed(rex_t* h, uint64_t seed) { if (!h) return set_err(REX_ERR_ARG, "null handle"); h->seed = seed; h->dev.seed = seed; return REX_OK; }
 
-static int do_reset(rex_t* h, const unsigned char* mask, int bit, int resample, int reset_state, float* obs, hipStream_t st) {
+// rows: obs is the caller's row-major [B][obs_dim] buffer (planar chains and cart-pole; the humanoid's reset always writes SoA, its rows go through rows.hpp)
+static int do_reset(rex_t* h, const unsigned char* mask, int bit, int resample, int reset_state, float* obs, hipStream_t st, bool rows = false) {
   const dim3 g = grid_for(h), b = lanes_of(h);
   if (resample && h->dr.type == REX_DR_NONE) return set_err(REX_ERR_STATE,
       "sampling value of random env needs to be set before using sample_task() or set_random_task()");   // random_env.py:201
   with_kind(h, [&](auto tag) {
     using Tag = decltype(tag);
     if constexpr (Tag::cartpole) {
-      hipLaunchKernelGGL(cartpole_reset_kernel, g, b, 0, st, h->dev, h->dr, resample, reset_state, mask, bit, obs);
+      if (rows) hipLaunchKernelGGL(cartpole_reset_kernel<true>, g, b, 0, st, h->dev, h->dr, resample, reset_state, mask, bit, obs);
+      else hipLaunchKernelGGL(cartpole_reset_kernel<false>, g, b, 0, st, h->dev, h->dr, resample, reset_state, mask, bit, obs);
     } else if constexpr (Tag::planar) {   // walker2d auto-reset under DR: the done bit becomes the pending bit, the derive launch below clears it
       using S = typename Tag::Spec;
-      hipLaunchKernelGGL(planar_reset_kernel<S>, g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs,
-                         (S::KIND == REX_WALKER2D && resample && mask == h->dev.done) ? DERIVE_PENDING_BIT : 0);
+      const int pending = (S::KIND == REX_WALKER2D && resample && mask == h->dev.done) ? DERIVE_PENDING_BIT : 0;
+      if (rows) hipLaunchKernelGGL((planar_reset_kernel<S, true>), g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs, pending);
+      else hipLaunchKernelGGL((planar_reset_kernel<S, false>), g, b, 0, st, h->dev, h->flags, h->dr, resample, reset_state, mask, bit, obs, pending);
     } else {
       launch_humanoid_reset(tag, h, resample, reset_state, mask, bit, obs, st);
     }
@@ -540,25 +569,30 @@ extern "C" int rex_set_random_task(rex_t* h, const uint8_t* mask, void* stream) 
   return do_reset(h, mask, 1, 1, 0, nullptr, (hipStream_t)stream);
 }
 
+// rows: action / obs / terminal obs are the caller's row-major buffers (the ROWS instantiation of the same shape: planar_kernels.hpp)
 template <class S>
 static void launch_planar_step(rex_env* h, const DevState& dev, const StepFlags& flags, const PlanarGeom<float, S>& geom, const float* action,
                                float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* truncated_out, float* terminal_obs_out,
-                               int fused, int resample, hipStream_t st) {
-  if (h->shape.pair) {   // 2 B lanes in blocks of pair_lanes: 32 envs per wave, fewer for a walker2d / half-cheetah batch of 8 192 .. 16 384 (choose_launch_shape)
-    const unsigned L = (unsigned)h->shape.pair_lanes, blocks = (unsigned)((2 * h->B + L - 1) / L);
-    hipLaunchKernelGGL((planar_step_kernel<S, true>), dim3(blocks), dim3(L), 0, st, dev, flags, geom, h->sp, action, obs_out, reward_out,
-                       done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
-  } else {
-    if constexpr (S::KIND == 1) {
-      if (h->shape.rolled) {   // two waves per SIMD (rex_create: more full waves than SIMDs)
-        hipLaunchKernelGGL((planar_step_kernel<S, false, true>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
-                           reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
-        return;
+                               int fused, int resample, hipStream_t st, bool rows = false) {
+  auto launch = [&](auto layout) {
+    constexpr bool ROWS = decltype(layout)::value;
+    if (h->shape.pair) {   // 2 B lanes in blocks of pair_lanes: 32 envs per wave, fewer for a walker2d / half-cheetah batch of 8 192 .. 16 384 (choose_launch_shape)
+      const unsigned L = (unsigned)h->shape.pair_lanes, blocks = (unsigned)((2 * h->B + L - 1) / L);
+      hipLaunchKernelGGL((planar_step_kernel<S, true, false, ROWS>), dim3(blocks), dim3(L), 0, st, dev, flags, geom, h->sp, action, obs_out, reward_out,
+                         done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
+    } else {
+      if constexpr (S::KIND == 1) {
+        if (h->shape.rolled) {   // two waves per SIMD (rex_create: more full waves than SIMDs)
+          hipLaunchKernelGGL((planar_step_kernel<S, false, true, ROWS>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
+                             reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
+          return;
+        }
       }
+      hipLaunchKernelGGL((planar_step_kernel<S, false, false, ROWS>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
+                         reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
     }
-    hipLaunchKernelGGL((planar_step_kernel<S, false>), grid_for(h), lanes_of(h), 0, st, dev, flags, geom, h->sp, action, obs_out,
-                       reward_out, done_out, truncated_out, terminal_obs_out, h->dr, fused, resample);
-  }
+  };
+  if (rows) launch(std::true_type{}); else launch(std::false_type{});
 }
 
 // The sampled event bracket of rex_step / rex_replay: every `timing`-th call is bracketed by two events of the pool rex_enable_timing
@@ -576,29 +610,99 @@ static int launch_timing_end(rex_env* h, hipStream_t st, const TimedCall& t) {
   return REX_OK;
 }
 
+// rex_step and rex_step_rows behind their argument checks: one step launch (bracketed by the sampled timing events), the masked reset launch when
+// the auto-reset is not fused.  rows: the caller's buffers are row-major -- the planar and cart-pole kernels take the layout themselves, the humanoid
+// runs its SoA kernels into the handle's staging between the action kernel and the transposer of rows.hpp.
+static int step_body(rex_env* h, const void* action, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* truncated_out, float* terminal_obs_out,
+                     hipStream_t st, bool rows) {
+  // planar envs reset finished lanes inside the step kernel (walker2d under DR re-derives the lane's geometry there as well)
+  const ResetPlan plan = reset_plan(h->kind, h->variant, h->autoreset, h->dr_training, h->dr.type, h->shape);
+  const void* k_action = action; float* k_obs = obs_out; float* k_term = terminal_obs_out;   // what the step (and reset) kernels see
+  bool staged = false;
+  int rc = REX_OK;
+  if (rows) with_kind(h, [&](auto tag) {
+    if constexpr (decltype(tag)::humanoid) {
+      staged = true;
+      rc = launch_rows_action(tag, h, (const float*)action, st);
+      k_action = hum_rows_action(tag, h); k_obs = hum_rows_obs(tag, h); k_term = terminal_obs_out ? hum_rows_term(tag, h) : nullptr;
+    }
+  });
+  if (rc) return rc;
+  const bool krows = rows && !staged;
+  TimedCall timed;
+  if ((rc = launch_timing_begin(h, st, &timed))) return rc;
+  with_kind(h, [&](auto tag) {
+    using Tag = decltype(tag);
+    if constexpr (Tag::cartpole) {
+      if (krows) hipLaunchKernelGGL(cartpole_step_kernel<true>, grid_for(h), lanes_of(h), 0, st, h->dev, h->flags, (const int*)k_action, k_obs, reward_out, done_out, truncated_out, k_term);
+      else hipLaunchKernelGGL(cartpole_step_kernel<false>, grid_for(h), lanes_of(h), 0, st, h->dev, h->flags, (const int*)k_action, k_obs, reward_out, done_out, truncated_out, k_term);
+    } else if constexpr (Tag::planar)
+      launch_planar_step<typename Tag::Spec>(h, h->dev, h->flags, tag.geom, (const float*)k_action, k_obs, reward_out, done_out, truncated_out, k_term, plan.fused, plan.rs, st, krows);
+    else
+      launch_humanoid_step(tag, h, h->dev, h->flags, (const float*)k_action, k_obs, reward_out, done_out, truncated_out, k_term, st, plan.fused, plan.resample);
+  });
+  if ((rc = launch_timing_end(h, st, timed))) return rc;
+  HIP_TRY(hipGetLastError());
+  h->step_count += h->B;
+  if (h->autoreset && !plan.fused && (rc = do_reset(h, h->dev.done, 2, plan.resample, 1, k_obs, st, krows))) return rc;
+  if (staged) with_kind(h, [&](auto tag) {
+    if constexpr (decltype(tag)::humanoid) rc = launch_rows_transpose(tag, h, obs_out, nullptr, 0, terminal_obs_out, done_out, st);
+  });
+  return rc;
+}
+
 extern "C" int rex_step(rex_t* h, const void* action, float* obs_out, float* reward_out, uint8_t* done_out,
                         uint8_t* truncated_out, float* terminal_obs_out, void* stream) {
   REX_ENTER(h, "rex_step");
   if (!action || !obs_out || !reward_out || !done_out) return set_err(REX_ERR_ARG, "rex_step: null buffer");
-  hipStream_t st = (hipStream_t)stream;
-  // planar envs reset finished lanes inside the step kernel (walker2d under DR re-derives the lane's geometry there as well)
-  const ResetPlan plan = reset_plan(h->kind, h->variant, h->autoreset, h->dr_training, h->dr.type, h->shape);
-  TimedCall timed;
-  if (int rc = launch_timing_begin(h, st, &timed)) return rc;
-  with_kind(h, [&](auto tag) {
-    using Tag = decltype(tag);
-    if constexpr (Tag::cartpole)
-      hipLaunchKernelGGL(cartpole_step_kernel, grid_for(h), lanes_of(h), 0, st, h->dev, h->flags, (const int*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out);
-    else if constexpr (Tag::planar)
-      launch_planar_step<typename Tag::Spec>(h, h->dev, h->flags, tag.geom, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, plan.fused, plan.rs, st);
-    else
-      launch_humanoid_step(tag, h, h->dev, h->flags, (const float*)action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, st, plan.fused, plan.resample);
-  });
-  if (int rc = launch_timing_end(h, st, timed)) return rc;
-  HIP_TRY(hipGetLastError());
-  h->step_count += h->B;
-  if (h->autoreset && !plan.fused) return do_reset(h, h->dev.done, 2, plan.resample, 1, obs_out, st);
+  return step_body(h, action, obs_out, reward_out, done_out, truncated_out, terminal_obs_out, (hipStream_t)stream, false);
+}
+
+// ------------------------------------------------------------------------------------------
+// the gym surface in the caller's row-major layout (rex.h "row-major calls")
+// ------------------------------------------------------------------------------------------
+static bool misaligned16(const void* p) { return p && ((uintptr_t)p & 15u) != 0; }
+
+extern "C" int rex_rows_enable(rex_t* h) {
+  REX_ENTER(h, "rex_rows_enable");
+  if (h->rows_enabled) return REX_OK;
+  size_t words = 0;   // only the humanoid stages anything
+  with_kind(h, [&](auto tag) { if constexpr (decltype(tag)::humanoid) words = ((size_t)h->dims.act_dim + 2 * (size_t)h->dims.obs_dim) * (size_t)h->B; });
+  if (words) {   // one block, so a failure leaves nothing to free; not cleared: the transposer reads only what the launches before it wrote
+    hipError_t e = hipMalloc(&h->rows_mem, sizeof(float) * words);
+    if (e != hipSuccess) { h->rows_mem = nullptr; return set_err(REX_ERR_HIP, "rex_rows_enable: staging allocation failed: %s", hipGetErrorString(e)); }
+  }
+  h->rows_enabled = 1;
   return REX_OK;
+}
+
+extern "C" int rex_reset_rows(rex_t* h, const uint8_t* mask, float* obs_rows, void* stream) {
+  REX_ENTER(h, "rex_reset_rows");
+  if (!obs_rows) return set_err(REX_ERR_ARG, "rex_reset_rows: null obs_rows");
+  if (h->kind == REX_HUMANOID) REX_NEEDS(h, rows_mem, "rex_reset_rows", "rex_rows_enable");
+  if (h->kind == REX_CARTPOLE && misaligned16(obs_rows)) return set_err(REX_ERR_ARG, "rex_reset_rows: obs_rows must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const ResetPlan plan = reset_plan(h->kind, h->variant, h->autoreset, h->dr_training, h->dr.type, h->shape);
+  int rc = REX_OK; bool staged = false;
+  with_kind(h, [&](auto tag) {
+    if constexpr (decltype(tag)::humanoid) {
+      staged = true;
+      rc = do_reset(h, mask, 1, plan.resample, 1, hum_rows_obs(tag, h), st);
+      if (rc == REX_OK) rc = launch_rows_transpose(tag, h, obs_rows, mask, 1, nullptr, nullptr, st);
+    }
+  });
+  if (staged) return rc;
+  return do_reset(h, mask, 1, plan.resample, 1, obs_rows, st, true);
+}
+
+extern "C" int rex_step_rows(rex_t* h, const void* action_rows, float* obs_rows, float* reward_out, uint8_t* done_out, uint8_t* truncated_out,
+                             float* terminal_obs_rows, void* stream) {
+  REX_ENTER(h, "rex_step_rows");
+  if (!action_rows || !obs_rows || !reward_out || !done_out) return set_err(REX_ERR_ARG, "rex_step_rows: null buffer");
+  if (h->kind == REX_HUMANOID) REX_NEEDS(h, rows_mem, "rex_step_rows", "rex_rows_enable");
+  if (h->kind == REX_CARTPOLE && (misaligned16(obs_rows) || misaligned16(terminal_obs_rows)))
+    return set_err(REX_ERR_ARG, "rex_step_rows: obs_rows / terminal_obs_rows must be 16-byte aligned");
+  return step_body(h, action_rows, obs_rows, reward_out, done_out, truncated_out, terminal_obs_rows, (hipStream_t)stream, true);
 }
 
 // Offline replay (random_hopper.py:128-152, random_half_cheetah.py:136-158, random_walker2d.py:161-185,

@@ -77,6 +77,9 @@ class NormalizedVecRandomEnv:
 
     def __init__(self, env, gamma=0.99, clip_obs=10.0, clip_reward=10.0, epsilon=1e-8, norm_obs=True, norm_reward=True, training=True):
         import torch
+        if getattr(env, "row_major", False):
+            raise ValueError("NormalizedVecRandomEnv needs an env in the default layout: its kernels read the env's SoA [obs_dim, batch] buffers, "
+                             "which a row_major=True env's step() does not write")
         self._torch = torch
         self.env = env
         self.gamma, self.clip_obs, self.clip_reward, self.epsilon = float(gamma), float(clip_obs), float(clip_reward), float(epsilon)

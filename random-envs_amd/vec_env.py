@@ -6,6 +6,10 @@ denormalize_parameters, load_dr_distribution_from_file) and the gym protocol of 
 (reset, step -> (obs, reward, done, info), get_task, set_task, seed).  All tensors are
 torch ROCm tensors; obs is ``[batch, obs_dim]`` (a zero-copy transposed view of the kernels'
 SoA ``[obs_dim][batch]`` buffer), reward ``[batch]`` f32, done ``[batch]`` bool.
+
+``row_major=True`` is the same surface with the kernels reading and writing the caller's layout: ``step`` takes a contiguous
+``[batch, act_dim]`` device tensor by pointer and returns contiguous ``[batch, obs_dim]`` observations and ``torch.bool`` flags in buffers the
+env owns, with no torch kernel in between (``rex_step_rows`` / ``rex_reset_rows``).
 """
 import ctypes
 
@@ -74,7 +78,7 @@ def make_spaces(dims):
 
 class VecRandomEnv(DRConfig):
     def __init__(self, kind, batch=1, device=0, seed=0, env_offset=0, noisy=False, env_id=None,
-                 autoreset=True, time_limit=True, unmodeled=False):
+                 autoreset=True, time_limit=True, unmodeled=False, row_major=False):
         import torch
         self._torch = torch
         self.unmodeled = bool(unmodeled)
@@ -110,6 +114,17 @@ class VecRandomEnv(DRConfig):
         self._info = torch.zeros(max(dims.n_info, 1), B, **f32) if dims.n_info else None
         if self._info is not None:
             _native.check(L.rex_set_info_buffer(self._h, ctypes.c_void_p(self._info.data_ptr())))
+        self.row_major = bool(row_major)
+        if self.row_major:   # the gym surface in the caller's layout: persistent [batch, dim] buffers the kernels write directly
+            _native.check(L.rex_rows_enable(self._h))
+            self._obs_rows = torch.zeros(B, dims.obs_dim, **f32)
+            self._term_rows = torch.zeros(B, dims.obs_dim, **f32)
+            self._done_b = torch.zeros(B, dtype=torch.bool, device=self.device)       # the kernels write bytes 0 / 1
+            self._trunc_b = torch.zeros(B, dtype=torch.bool, device=self.device)
+            self._act_rows = torch.zeros(B, dtype=torch.int32, device=self.device) if dims.discrete_action else torch.zeros(B, dims.act_dim, **f32)
+            self._info_rows = {"TimeLimit.truncated": self._trunc_b, "terminal_observation": self._term_rows}
+            for k, name in enumerate(self.INFO_TERMS[self.kind]):
+                self._info_rows[name] = self._info[k]
         self._draws = 0
         self._push_flags()
 
@@ -373,11 +388,39 @@ class VecRandomEnv(DRConfig):
         return ctypes.c_void_p(self._mask.data_ptr())
 
     def reset(self, mask=None):
+        """Row-major mode: returns the env's own ``[batch, obs_dim]`` buffer (rows of unmasked envs are not written)."""
         m = self._mask_ptr(mask)
+        if self.row_major:
+            _native.check(self._L.rex_reset_rows(self._h, m, ctypes.c_void_p(self._obs_rows.data_ptr()), self._stream()))
+            return self._obs_rows
         _native.check(self._L.rex_reset(self._h, m, ctypes.c_void_p(self._obs.data_ptr()), self._stream()))
         return self._obs.t()
 
+    def _step_rows(self, action):
+        t = self._torch
+        want = self._act_rows
+        if (isinstance(action, t.Tensor) and action.device == want.device and action.dtype == want.dtype and action.is_contiguous()
+                and action.shape == want.shape):
+            a = action                        # read by pointer: no copy, no torch kernel
+        else:                                 # numpy, lists, other dtypes / devices / strides: one copy_ into the owned buffer
+            src = action if isinstance(action, t.Tensor) else t.as_tensor(np.asarray(action))
+            want.copy_(src.reshape(want.shape))
+            a = want
+        p = lambda z: ctypes.c_void_p(z.data_ptr())
+        _native.check(self._L.rex_step_rows(self._h, p(a), p(self._obs_rows), p(self._reward), p(self._done_b), p(self._trunc_b),
+                                            p(self._term_rows), self._stream()))
+        return self._obs_rows, self._reward, self._done_b, dict(self._info_rows)
+
     def step(self, action):
+        """``(obs, reward, done, info)`` of one step of every env (auto-reset inside, ``info["terminal_observation"]`` on the done rows).
+
+        Row-major mode (``row_major=True``): a contiguous float32 (CartPole: int32) tensor of shape ``[batch, act_dim]`` (``[batch]``) on
+        the env's device is read by pointer; anything else takes one ``copy_`` into an owned buffer.  ``obs`` ``[batch, obs_dim]``,
+        ``reward``, ``done`` (``torch.bool``), ``info["TimeLimit.truncated"]`` and ``info["terminal_observation"]`` are buffers the env
+        owns: THE NEXT CALL OVERWRITES THEM (clone what has to outlive it; in the default mode ``done`` is a fresh tensor each call).
+        ``terminal_observation`` is defined on the rows whose ``done`` is set; its other rows keep what they held."""
+        if self.row_major:
+            return self._step_rows(action)
         t = self._torch
         a = t.as_tensor(action, device=self.device)
         if self.dims.discrete_action:
