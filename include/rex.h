@@ -200,7 +200,9 @@ int rex_export_lane(rex_t* h, int64_t lane, float* qpos /*[host, nq]*/, float* q
 /* number of env-steps executed by this handle (host counter; the only quantity the multi-GPU
  * path reduces across ranks). */
 int64_t rex_step_count(const rex_t* h);
-/* device-side diagnostics accumulated since creation: [0] lanes that went non-finite,
+/* device-side diagnostics accumulated since creation: [0] lane-steps that left a non-finite element in qpos or qvel -- in every kind such a
+ * step returns terminated = 1 and TimeLimit.truncated = 0, under set_endless as well, so the auto-reset restarts the lane; with the auto-reset
+ * off the lane stays done and is counted once per step (rex_replay counts nothing); a non-finite action that leaves the state finite is not counted,
  * [1] gaussian-DR draws that failed the reference's 3-attempt rule (random_env.py:173-190),
  * [2] constraint solves that hit the iteration cap. Copies 4 int64 to `out` [host]; synchronises. */
 int rex_get_counters(rex_t* h, int64_t* out);

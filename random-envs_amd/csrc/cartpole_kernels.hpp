@@ -29,7 +29,10 @@ __global__ void __launch_bounds__(64) cartpole_step_kernel(DevState s, StepFlags
   s.qpos[i] = x; s.qpos[B + i] = th; s.qvel[i] = xd; s.qvel[B + i] = thd;
   const float th_thr = 12.0f * 2.0f * 3.14159265358979323846f / 360.0f, x_thr = 2.4f;   // :84-85
   bool was_done = s.done[i] != 0;                          // steps_beyond_done bookkeeping :208-222
-  bool dn = (x < -x_thr) || (x > x_thr) || (th < -th_thr) || (th > th_thr);
+  // (every comparison of the rule is false on a NaN: a non-finite lane ends its episode and is counted, as in every other kind -- rex.h, rex_get_counters)
+  const bool finite = isfinite(x) && isfinite(th) && isfinite(xd) && isfinite(thd);
+  bool dn = (x < -x_thr) || (x > x_thr) || (th < -th_thr) || (th > th_thr) || !finite;
+  if (!finite) atomicAdd(s.counters + 0, 1ull);
   float r = (!dn) ? 1.0f : (was_done ? 0.0f : 1.0f);
   int t = s.t[i] + 1; s.t[i] = t;
   bool trunc = fl.time_limit && t >= fl.max_steps && !dn;

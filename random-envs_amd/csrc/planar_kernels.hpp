@@ -192,11 +192,12 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
     static_for<0, S::NV>([&](auto KK) { constexpr int k = KK; small = small && fabsf(v[k]) < 100.0f; });
     dn = !(finite && small && q[1] > 0.7f && fabsf(q[2]) < 0.2f);
   } else if constexpr (S::KIND == 3) {   // random_walker2d.py:124-125
-    dn = !(q[1] > 0.8f && q[1] < 2.0f && q[2] > -1.0f && q[2] < 1.0f);
+    dn = !(q[1] > 0.8f && q[1] < 2.0f && q[2] > -1.0f && q[2] < 1.0f) || !finite;
   } else {                               // random_half_cheetah.py:108
-    dn = false;
+    dn = !finite;
   }
-  if (fl.endless) dn = false;            // random_hopper.py:95-96
+  // a non-finite lane ends its episode in every kind and whatever `endless` says (rex.h, rex_get_counters): the hopper's own rule has the clause
+  if (fl.endless && finite) dn = false;  // random_hopper.py:95-96
   if (!fl.readonly) {   // (rex_replay: nothing of the handle is written, its counters included)
     if (!finite) atomicAdd(s.counters + 0, 1ull);
     if (capped && threadIdx.x == 0) atomicAdd(s.counters + 2, 1ull);
