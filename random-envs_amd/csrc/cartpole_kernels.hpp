@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(64) cartpole_reset_kernel(DevState s, DRParams
   const long long B = s.B;
   unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
   rocrand_state_philox4x32_10 st;
-  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
+  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_episode(ep), &st);
   if (reset_state) {
     float v[4];
 #pragma unroll
@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(64) cartpole_reset_kernel(DevState s, DRParams
     }
   }
   if (resample && dr.type != REX_DR_NONE) {
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, i, s.counters);
+    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), philox_task(ep), s.xi, (size_t)B, i, s.counters);
   }
 }
 

@@ -33,7 +33,12 @@ struct DRParams {
 // observation noise of step t.  2^32 offsets per episode keep the step regions of consecutive episodes disjoint for
 // 2^26 steps (time_limit off / endless episodes run far past 500 steps); the Philox counter is 64-bit + 64-bit subsequence.
 constexpr unsigned long long EP_STRIDE = 1ull << 32;
-constexpr unsigned long long STEP_BASE = 512, STEP_STRIDE = 64;
+constexpr unsigned long long XI_BASE = 256, STEP_BASE = 512, STEP_STRIDE = 64;
+// the three offsets the kernels form (tests/rng_oracle.py restates them): the base of episode ep (= its init-state noise), the xi draws
+// of its reset, the observation noise of its step t (t = 0: the reset observation)
+constexpr unsigned long long philox_episode(unsigned ep) { return (unsigned long long)ep * EP_STRIDE; }
+constexpr unsigned long long philox_task(unsigned ep) { return (unsigned long long)ep * EP_STRIDE + XI_BASE; }
+constexpr unsigned long long philox_step(unsigned ep, int t) { return (unsigned long long)ep * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE; }
 constexpr unsigned long long SAMPLE_SEED_SALT = 0x9E3779B97F4A7C15ull;   // rex_sample_task: a stream family of its own
 
 // truncated standard normal on [-2, 2] by inverse CDF (the method scipy.stats.truncnorm.rvs uses)

@@ -2,12 +2,14 @@
 //
 // The default step is humanoid_pair_step_kernel: TWO LANES PER ENV (humanoid_pair.hpp; 32 envs per 64-lane block, every lane active), the
 // env's dual PGS working set and hit queue in one LDS column, the auto-reset of finished envs fused into the launch.  Its body is four
-// calls into humanoid_pair.hpp -- load_lane, env_step, store_lane, reset_lane: which lane holds which row of the state is said there, once,
-// and the host harness runs the same functions -- plus what is not layout: Philox set-up, done logic, counters, outputs.  humanoid_step_kernel
-// is the hum_pair = 0 shape (REX_HUM_PAIR=0): one env per lane over humanoid_engine.hpp, which the reset and forward kernels use at every
-// setting.  There the per-lane working set of a forward evaluation (hum::Scratch, ~20 KB: M 23x23, J and M^-1 J^T for up to 64 rows) lives
-// in HIP scratch memory, lane-interleaved so every access of a wave is one coalesced segment.  The compiled model is uniform and sits in
-// __constant__ memory.
+// calls into humanoid_pair.hpp -- load_lane, store_lane, reset_lane (humanoid_pair_lanes.hpp: which lane holds which row of the state is said
+// there, once) and env_step (humanoid_pair_step.hpp); the host harness runs the same functions -- plus what is not layout: Philox set-up
+// (the offsets are device_rng.hpp's philox_episode / philox_task / philox_step), done logic, counters, outputs.  humanoid_step_kernel is the
+// hum_pair = 0 shape (REX_HUM_PAIR=0): one env per lane over humanoid_engine.hpp (env_step and env_reset_obs: humanoid_step.hpp), which the
+// reset and forward kernels use at every setting.  Both engine headers are umbrellas over one header per layer (listed at their top).
+// In the one-lane shape the per-lane working set of a forward evaluation (hum::Scratch, ~20 KB: M 23x23, J and M^-1 J^T for up to 64 rows)
+// lives in HIP scratch memory, lane-interleaved so every access of a wave is one coalesced segment.  The compiled model is uniform and sits
+// in __constant__ memory.
 #pragma once
 #include "device_rng.hpp"
 #include "humanoid_model.hpp"
@@ -31,6 +33,14 @@ __device__ __forceinline__ void hum_obs_noise(const DevState& s, const StepFlags
   for (int k = 0; k < 45; k++) nz[k] = fl.noise_std * rocrand_normal(&st);
 }
 
+// qpos / qvel rows of env i of the SoA state, one lane per env (the step and forward kernels).  The write-back of the step and reset kernels
+// stays written out in each: as a function it changed both kernels' code (profiles/HISTORY.md).
+__device__ __forceinline__ void hum_load_state(const DevState& s, unsigned i, float (&q)[hum::NQ], float (&v)[hum::NV]) {
+  const size_t B = (size_t)s.B;
+  for (int k = 0; k < hum::NQ; k++) q[k] = (s.qpos + k * B)[i];
+  for (int k = 0; k < hum::NV; k++) v[k] = (s.qvel + k * B)[i];
+}
+
 __global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags fl, const float* __restrict__ action,
                                                            float* __restrict__ obs, float* __restrict__ reward,
                                                            unsigned char* __restrict__ done_out, unsigned char* __restrict__ trunc_out,
@@ -40,8 +50,7 @@ __global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags
   const size_t B = (size_t)s.B;
   hum::Lane<float> L; hum_lane(s, i, L);
   float q[hum::NQ], v[hum::NV], a[hum::NU], xp[hum::NBODY];
-  for (int k = 0; k < hum::NQ; k++) q[k] = (s.qpos + k * B)[i];
-  for (int k = 0; k < hum::NV; k++) v[k] = (s.qvel + k * B)[i];
+  hum_load_state(s, i, q, v);
   for (int k = 0; k < hum::NU; k++) a[k] = (action + k * B)[i];
   for (int b = 0; b < hum::NBODY; b++) xp[b] = (s.aux + b * B)[i];
   hum::Kin<float> kn; hum::Scratch<float> sc;
@@ -49,8 +58,7 @@ __global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags
   float r; bool dn;
   rocrand_state_philox4x32_10 st;
   int t = s.t[i] + 1;
-  if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i),
-                             (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, &st);
+  if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_step(s.episode[i], t), &st);
   REX_WSTAMP(tk0);
   float terms[4];
   hum::env_step(c_hum, L, q, v, a, xp, kn, sc, r, dn, [&](int k, float val) {
@@ -64,6 +72,7 @@ __global__ void __launch_bounds__(64) humanoid_step_kernel(DevState s, StepFlags
   bool finite = true;
   for (int k = 0; k < hum::NQ; k++) finite = finite && isfinite(q[k]);
   for (int k = 0; k < hum::NV; k++) finite = finite && isfinite(v[k]);
+  // (the verdict and its writes are humanoid_pair_step_kernel's, there under !left; here the state rows go out between t and done)
   if (!finite) dn = true;                                           // a diverged lane ends its episode
   if (fl.endless && finite) dn = false;
   bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;
@@ -141,12 +150,13 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
       if (dst2) (dst2 + row * B)[i] = val;
     });
   };
-  if (fl.noisy) hum_obs_noise(s, fl, i, (unsigned long long)s.episode[i] * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE, nz);
+  if (fl.noisy) hum_obs_noise(s, fl, i, philox_step(s.episode[i], t), nz);
   put_obs(obs, term_obs);
   bool finite = true;
   static_for<0, pr::LQ>([&](auto KK) { finite = finite && isfinite(ql[KK]); });
   static_for<0, pr::LD>([&](auto KK) { finite = finite && isfinite(vl[KK]); });
   finite = finite && (p.xchg(finite ? 1u : 0u) != 0u);
+  // (the verdict and its writes are humanoid_step_kernel's; both lanes need d for the fused reset, the right lane writes)
   if (!finite) dn = true;                                           // a diverged lane ends its episode
   if (fl.endless && finite) dn = false;
   const bool trunc = fl.time_limit && t >= fl.max_steps && !dn && !fl.readonly;
@@ -170,16 +180,16 @@ __global__ void __launch_bounds__(64) humanoid_pair_step_kernel(DevState s, Step
   if (fused_reset && d) {
     const unsigned ep = s.episode[i] + 1;
     rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
+    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_episode(ep), &st);
     pr::reset_lane(p, c_hum, L, [&]() { return rocrand_uniform(&st); }, ql, vl, xp, park);
-    if (fl.noisy) hum_obs_noise(s, fl, i, (unsigned long long)ep * EP_STRIDE + STEP_BASE, nz);
+    if (fl.noisy) hum_obs_noise(s, fl, i, philox_step(ep, 0), nz);
     put_obs(obs, nullptr);
     pr::store_lane(left, wr, ql, vl, xp);
     if (!left) {
       s.episode[i] = ep;
       s.t[i] = 0; s.done[i] = 0;
       if (resample && dr.type != REX_DR_NONE)
-        sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, B, i, s.counters);
+        sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), philox_task(ep), s.xi, B, i, s.counters);
     }
   }
 }
@@ -196,7 +206,7 @@ __global__ void __launch_bounds__(64) humanoid_reset_kernel(DevState s, StepFlag
   const size_t B = (size_t)s.B;
   unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
   rocrand_state_philox4x32_10 st;
-  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
+  rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_episode(ep), &st);
   if (reset_state) {
     float q[hum::NQ], v[hum::NV], xp[hum::NBODY];
     for (int k = 0; k < hum::NQ; k++) q[k] = c_hum.qpos0[k] + 0.01f * (2.0f * (1.0f - rocrand_uniform(&st)) - 1.0f);
@@ -204,7 +214,7 @@ __global__ void __launch_bounds__(64) humanoid_reset_kernel(DevState s, StepFlag
     hum::Lane<float> L; hum_lane(s, i, L);
     hum::Kin<float> kn; hum::Scratch<float> sc;
     rocrand_state_philox4x32_10 st2;
-    if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
+    if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_step(ep, 0), &st2);
     hum::env_reset_obs(c_hum, L, q, v, xp, kn, sc, [&](int k, float val) {
       if (fl.noisy && k < 45) val += fl.noise_std * rocrand_normal(&st2);
       if (obs) (obs + k * B)[i] = val;
@@ -215,7 +225,7 @@ __global__ void __launch_bounds__(64) humanoid_reset_kernel(DevState s, StepFlag
     s.t[i] = 0; s.done[i] = 0;
   }
   if (resample && dr.type != REX_DR_NONE) {
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, B, i, s.counters);
+    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), philox_task(ep), s.xi, B, i, s.counters);
   }
 }
 
@@ -225,8 +235,7 @@ __global__ void __launch_bounds__(64) humanoid_forward_kernel(DevState s, float*
   if (i >= s.B) return;
   const size_t B = (size_t)s.B;
   float q[hum::NQ], v[hum::NV], xp[hum::NBODY];
-  for (int k = 0; k < hum::NQ; k++) q[k] = (s.qpos + k * B)[i];
-  for (int k = 0; k < hum::NV; k++) v[k] = (s.qvel + k * B)[i];
+  hum_load_state(s, i, q, v);
   hum::Lane<float> L; hum_lane(s, i, L);
   hum::Kin<float> kn; hum::Scratch<float> sc;
   hum::env_reset_obs(c_hum, L, q, v, xp, kn, sc, [&](int k, float val) { if (obs) (obs + k * B)[i] = val; });

@@ -76,7 +76,7 @@ __device__ __forceinline__ void reset_state_values(unsigned long long seed, unsi
   constexpr int NV = S::NV;
   constexpr int NW = S::KIND == 2 ? 4 * (NV / 2) + (NV % 2 ? 3 : 0) : 2 * NV, NBLK = (NW + 3) / 4;
   unsigned w[4 * NBLK];
-  philox_blocks<NBLK>(seed, subseq, ((unsigned long long)ep * EP_STRIDE) >> 2, w);
+  philox_blocks<NBLK>(seed, subseq, philox_episode(ep) >> 2, w);
   const float c = S::INIT_NOISE;
   if constexpr (S::KIND == 2) {
     static_for<0, (NV + 1) / 2>([&](auto PP) { constexpr int p = PP;
@@ -211,7 +211,7 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
   const unsigned long long subseq = (unsigned long long)(s.env_offset + io);
   float ob[S::NOBS];
   obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq,
-                (unsigned long long)ep_prev * EP_STRIDE + STEP_BASE + (unsigned long long)t * STEP_STRIDE);
+                philox_step(ep_prev, t));
   // what always carries the STEPPED values goes out first
   // (row-major: the terminal observation is defined on the done rows and only those are written, rex.h)
   if (term_obs && (!ROWS || d)) static_for<0, S::NOBS>([&](auto KK) { constexpr int k = KK;
@@ -231,13 +231,13 @@ planar_step_kernel(DevState s, StepFlags fl, PlanarGeom<float, S> ugeom,
     REX_WTAIL_MAX(2, tr0);
     reset_state_values<S>(s.seed, subseq, ep, q, v);
     t = 0; dflag = 0;
-    obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + STEP_BASE);
+    obs_values<S>(q, v, ob, fl.noisy != 0, fl.noise_std, s.seed, subseq, philox_step(ep, 0));
     REX_WTAIL_MAX(3, tr0);
     if ((resample & RS_RESAMPLE) && dr.type != REX_DR_NONE) {
       // separate stream region so the xi draw does not depend on the state draws.  truncnorm / gaussian consume a data-dependent number
       // of words (redraw rules) and fullgaussian replays the stream per dimension: they take their words from PhiloxWords
-      if (dr.type == REX_DR_UNIFORM && dr.dim <= S::NXI) sample_task_uniform<S::NXI>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io);
-      else sample_task<PhiloxWords>(dr, s.seed, subseq, (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, io, s.counters);
+      if (dr.type == REX_DR_UNIFORM && dr.dim <= S::NXI) sample_task_uniform<S::NXI>(dr, s.seed, subseq, philox_task(ep), s.xi, (size_t)B, io);
+      else sample_task<PhiloxWords>(dr, s.seed, subseq, philox_task(ep), s.xi, (size_t)B, io, s.counters);
     }
     REX_WTAIL_MAX(4, tr0);
     if constexpr (S::KIND == 3) {   // (reads the new xi lengths back behind their stores)
@@ -268,7 +268,7 @@ __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepF
   unsigned ep = s.episode[i] + 1; s.episode[i] = ep;
   if (reset_state) {
     rocrand_state_philox4x32_10 st;
-    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE, &st);
+    rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_episode(ep), &st);
     float q[S::NV], v[S::NV];
     const float c = S::INIT_NOISE;
     static_for<0, S::NV>([&](auto KK) { constexpr int k = KK;
@@ -281,13 +281,13 @@ __device__ __forceinline__ void planar_reset_lane(const DevState& s, const StepF
     s.t[i] = 0; s.done[i] = 0;
     if (obs) {
       rocrand_state_philox4x32_10 st2;
-      if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + STEP_BASE, &st2);
+      if (fl.noisy) rocrand_init(s.seed, (unsigned long long)(s.env_offset + i), philox_step(ep, 0), &st2);
       write_obs<S, ROWS>(q, v, obs, B, i, fl.noisy != 0, fl.noise_std, &st2);
     }
   }
   if (resample && dr.type != REX_DR_NONE) {
     // separate stream region so the xi draw does not depend on reset_state
-    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), (unsigned long long)ep * EP_STRIDE + 256, s.xi, (size_t)B, i, s.counters);
+    sample_task(dr, s.seed, (unsigned long long)(s.env_offset + i), philox_task(ep), s.xi, (size_t)B, i, s.counters);
   }
 }
 

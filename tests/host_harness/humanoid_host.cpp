@@ -20,7 +20,7 @@ template <class T> static void lane_from_xi(const Model<T>& m, const double* xi,
 
 template <class T>
 static void run_step(int n, const double* qpos, const double* qvel, const double* act, const double* xi, const double* xprev,
-                     double* qpos_out, double* qvel_out, double* obs, double* reward, unsigned char* done, double* xout, int* overflow) {
+                     double* qpos_out, double* qvel_out, double* obs, double* reward, unsigned char* done, double* xout, int* overflow, int* nrows) {
   Ctx<T>* c = ctx<T>();
   for (int i = 0; i < n; i++) {
     Lane<T> L; lane_from_xi(c->m, xi + i, n, L);
@@ -34,7 +34,7 @@ static void run_step(int n, const double* qpos, const double* qvel, const double
     env_step(c->m, L, q, v, a, xp, c->k, c->s, r, d, [&](int k, T val) { obs[(size_t)k * n + i] = double(val); });
     for (int k = 0; k < NQ; k++) qpos_out[(size_t)k * n + i] = double(q[k]);
     for (int k = 0; k < NV; k++) qvel_out[(size_t)k * n + i] = double(v[k]);
-    reward[i] = double(r); done[i] = d; if (overflow) overflow[i] = c->k.overflow;
+    reward[i] = double(r); done[i] = d; if (overflow) overflow[i] = c->k.overflow; if (nrows) nrows[i] = c->k.nefc;
     if (xout) for (int b = 0; b < NBODY; b++) xout[(size_t)b * n + i] = double(xp[b]);
   }
 }
@@ -65,11 +65,17 @@ int hh_constants(double* mass, double* invw_body, double* invw_dof, double* ipos
   *npair = c->m.npair;
   return 0;
 }
+// nrows: constraint rows of the step's LAST forward evaluation (stage 4 of the fifth frame), as hp_step reports them
+int hh_step_rows(int f32, int n, const double* qpos, const double* qvel, const double* act, const double* xi, const double* xprev,
+                 double* qpos_out, double* qvel_out, double* obs, double* reward, unsigned char* done, double* xout, int* overflow, int* nrows) {
+  if (f32) run_step<float>(n, qpos, qvel, act, xi, xprev, qpos_out, qvel_out, obs, reward, done, xout, overflow, nrows);
+  else run_step<double>(n, qpos, qvel, act, xi, xprev, qpos_out, qvel_out, obs, reward, done, xout, overflow, nrows);
+  return 0;
+}
+// (the 14-argument form the older tests call: a caller that passes no row-count pointer must not have one read off its stack)
 int hh_step(int f32, int n, const double* qpos, const double* qvel, const double* act, const double* xi, const double* xprev,
             double* qpos_out, double* qvel_out, double* obs, double* reward, unsigned char* done, double* xout, int* overflow) {
-  if (f32) run_step<float>(n, qpos, qvel, act, xi, xprev, qpos_out, qvel_out, obs, reward, done, xout, overflow);
-  else run_step<double>(n, qpos, qvel, act, xi, xprev, qpos_out, qvel_out, obs, reward, done, xout, overflow);
-  return 0;
+  return hh_step_rows(f32, n, qpos, qvel, act, xi, xprev, qpos_out, qvel_out, obs, reward, done, xout, overflow, nullptr);
 }
 int hh_check_topology() { Model<double> md; build_model(md); return check_topology(md) ? 1 : 0; }
 int hh_forward(int f32, const double* qpos, const double* qvel, const double* ctrl, const double* xi, double* qacc, double* M, int* info) {

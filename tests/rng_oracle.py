@@ -25,6 +25,7 @@ import numpy as np
 
 from replay_buffer_oracle import M32, philox4x32_10
 
+# the layout of device_rng.hpp: philox_episode(ep) = ep * EP_STRIDE + INIT_BASE, philox_task(ep) = ... + XI_BASE, philox_step(ep, t) = ... + STEP_BASE + t * STEP_STRIDE
 EP_STRIDE = 1 << 32
 INIT_BASE, XI_BASE, STEP_BASE, STEP_STRIDE = 0, 256, 512, 64
 INIT_WORDS, XI_WORDS, STEP_WORDS, SAMPLE_WORDS = 256, 256, 64, 256     # the budget of each region
