@@ -28,7 +28,7 @@ void launch(long long n, int block, F&& thread) {
     }
 }
 
-// launch_per_refresh of rex_hip.hip: one launch per level below the top two, then the single block
+// launch_per_refresh of abi_replay.hpp: one launch per level below the top two, then the single block
 void refresh(const Buf& b, const long long* index, long long n, long long s0, long long s1) {
   for (int l = 1; l < top_first_level(b.tr); l++) {
     const long long first = index ? 0 : range_first(s0, l), count = index ? n : range_count(s0, s1, l);

@@ -49,12 +49,21 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 _CSRC = os.path.join(ROOT, "random-envs_amd", "csrc")
 _SRC = os.path.join(_CSRC, "rex_hip.hip")
 _DEVICE_WORK = re.compile(r"hipLaunchKernelGGL|hipMemcpy|hipMemset|hipDeviceSynchronize|hipEvent(Record|Create|Synchronize)|hipMalloc|hipFree|"
-                          r"\bcopy_rows\(|\bdo_reset\(|\blaunch_[a-z_]+(<[A-Za-z0-9_: ]+>)?\(|\bensure_replay_scratch\(|\bwith_kind\(")
+                          r"\bcopy_rows\(|\bdo_reset\(|\blaunch_[a-z_]+(<[A-Za-z0-9_: ]+>)?\(|\bensure_replay_scratch\(|\bwith_kind\(|"
+                          r"\bread_counters\(|\bsample_call\(|\bwith_layout\(")
+
+
+def _host_layer():
+    """the host side of the C-ABI as one text: rex_hip.hip followed by the abi_*.hpp family headers it includes, in include order"""
+    src = open(_SRC).read()
+    families = re.findall(r'^#include "(abi_[a-z_]+\.hpp)"', src, flags=re.M)
+    assert len(families) >= 5 and sorted(families) == sorted(os.path.basename(p) for p in glob.glob(os.path.join(_CSRC, "abi_*.hpp")))
+    return src + "".join(open(os.path.join(_CSRC, f)).read() for f in families)
 
 
 def _exported_bodies():
-    """name -> body of every extern "C" function defined in rex_hip.hip (brace matching; diagnostic-only rex_debug_* excluded)."""
-    src = open(_SRC).read()
+    """name -> body of every extern "C" function defined in the host layer (brace matching; diagnostic-only rex_debug_* excluded)."""
+    src = _host_layer()
     out = {}
     for m in re.finditer(r'extern "C"\s+[^;{(]*?\b(rex_[a-z_0-9]+)\s*\(([^)]*)\)\s*\{', src):
         depth, i = 1, m.end()
@@ -70,7 +79,7 @@ def test_every_entry_point_that_touches_the_device_selects_the_handles_device_fi
     launches, copies, allocates or synchronises must make the handle's device current BEFORE it does (REX_ENTER, or hipSetDevice(h->device)
     ahead of the first such call).  Round 3 shipped half of them without it -- invisible on a one-GPU box."""
     bodies = _exported_bodies()
-    assert len(bodies) >= 30
+    assert len(bodies) >= 77
     missing = []
     for name, (args, body) in bodies.items():
         if "rex_t*" not in args.replace("rex_t *", "rex_t*") or "rex_t**" in args.replace(" ", ""):
@@ -82,7 +91,7 @@ def test_every_entry_point_that_touches_the_device_selects_the_handles_device_fi
         if not sel or sel.start() > work.start():
             missing.append(name)
     assert not missing, "entry points that touch the device before selecting it: %s" % missing
-    create = open(_SRC).read()
+    create = _host_layer()
     assert re.search(r"HIP_TRY\(hipSetDevice\(device_id\)\);\s*rex_env\* h = new", create), "rex_create selects device_id before allocating"
 
 
@@ -90,7 +99,7 @@ def test_the_product_reads_no_environment_variable_outside_the_gated_knobs():
     """A stray variable must not change what a production process computes: every getenv of the library sits in the three knob helpers
     (honoured only beside REX_ALLOW_TUNING=1, refused by rex_create otherwise), the physics-changing diagnostics are compiled in by -DREX_TUNING
     only, and build() never defines it."""
-    src = open(_SRC).read()
+    src = _host_layer()
     headers = glob.glob(os.path.join(_CSRC, "*.hpp"))
     assert len(headers) >= 6
     for inc in headers:
@@ -129,7 +138,7 @@ def test_probe_switches_live_in_probes_hpp_and_dead_switches_are_gone():
 def test_rex_create_has_one_cleanup_path():
     """Every failure after the handle exists goes through rex_destroy (which frees whatever was allocated): create_body only RETURNS error
     codes, rex_create destroys the handle on any of them, and the humanoid's process-wide model is a thread-safe magic static."""
-    src = open(_SRC).read()
+    src = _host_layer()
     body = src[src.index("static int create_body("):src.index('extern "C" int rex_create(')]
     assert "delete h" not in body and "new (std::nothrow) rex_env" not in body
     create = _exported_bodies()["rex_create"][1]
@@ -141,7 +150,7 @@ def test_the_launch_shape_rule_and_the_kind_dispatch_exist_once():
     """The launch-shape rule is csrc/launch_shape.hpp -- pure host code (no HIP include; the getenv test above covers its environment
     access) that holds every threshold, while the handle keeps one LaunchShape and no loose shape field -- and rex_hip.hip asks which env
     kinds a build compiles in with_kind, the humanoid block and the walker2d derive launch only."""
-    src = open(_SRC).read()
+    src = _host_layer()
     rule = open(os.path.join(_CSRC, "launch_shape.hpp")).read()
     assert "hip" not in re.sub(r"//.*", "", rule).lower() and '#include "' not in rule.replace('#include "../../include/rex.h"', "")
     for threshold in ("32ll * simds", "64ll * simds", "8ll * simds", "524288"):
