@@ -619,6 +619,57 @@ int rex_per_sample_seq(rex_t* h, const rex_rbuf_buffers* rbuf, const rex_per_buf
                        uint64_t draw, int seq_len, int normalise, float* obs_out, void* action_out, float* reward_out, float* done_out,
                        float* mask_out, int32_t* length_out, int64_t* index_out, float* prob_out, void* stream);
 
+/* ---- acting-time history: a mirrored ring of (observation, previous action) frames -------------------------------------------------
+ * The other half of the sequence windows above: at ACTING time a recurrent or history-fed policy needs the last K frames of every env
+ * (stable-baselines3's VecFrameStack is the CPU counterpart).  An opt-in layer beside the others: rex_step, rex_norm_*, rex_rollout_*,
+ * rex_rbuf_*, rex_per_* and rex_eplog_* are untouched, and there is no enable call -- the handle contributes its batch B, obs_dim,
+ * act_dim and the action type only.  No rex_hist_* call allocates, synchronises or keeps host state between calls; each is ONE launch
+ * on `stream`, so a captured revolution of K steps replays.
+ *
+ * Storage is caller-owned device memory, batch-first like the outputs of the sequence calls:
+ *   frames [B][2K][W] f32   W = obs_dim + (with_action ? act_dim : 0).  A frame is the observation row followed by the action that led
+ *                           to it; the cart-pole's int32 action is converted, (float)a (a frame is network input, not a bit copy).
+ *   length [B] int32        valid frames of the lane's window, saturating at K
+ *   K                       an int in [1, 64], the range of seq_len
+ * All envs step in lockstep, so one ring position serves the batch.  A push at slot c (0 <= c < K) writes the new frame to rows c and
+ * c + K: rows r and r + K of a lane are always equal.  Before the push the lane's window is rows [c, c + K - 1]; after it rows
+ * [c + 1, c + K], oldest first, newest last, of which the first K - length[b] are zero.  frames[:, c + 1 : c + K + 1, :] is therefore a
+ * zero-copy [B][K][W] view with strides (2KW, W, 1), and a step writes 2 W words per env where a shift moves (2K - 1) W.  The caller
+ * passes slot = (number of pushes so far) mod K, as t in rex_rollout_add.
+ *
+ * Input layout: rows == 0 -- obs / terminal_obs [obs_dim][B] and action [act_dim][B], as rex_step reads and writes them; rows != 0 --
+ * [B][obs_dim] and [B][act_dim], as rex_step_rows does.  The cart-pole's action is int32 [B] either way.
+ *
+ * rex_hist_push, for every lane b, in this order:
+ *   1. if done != NULL && done[b] (the lane was auto-reset; obs[b] is the first observation of its next episode):
+ *        with term_out, term_out[b][k] = frames[b][slot + 1 + k] for k = 0 .. K - 2 and term_out[b][K - 1] = (terminal_obs[b], action[b]):
+ *        the window the finished episode would have seen, which a history-fed critic bootstraps a time-limit end from.  Rows of term_out
+ *        whose done is clear are left as they were.  Then all 2K rows of the lane become 0 and length[b] = 0.
+ *   2. frame = (obs[b], with_action ? (done lane ? 0 : action[b]) : nothing); rows slot and slot + K take it; length[b] = min(length[b] + 1, K).
+ * rex_hist_reset is the companion of rex_reset: slot is the slot of the most recent push (any slot after rex_hist_init or for a full
+ *   reset; the next push then goes to slot + 1, as after a push).  The lanes with mask[b] != 0 (all when mask == NULL) are cleared,
+ *   their frame (obs[b], zeros) goes to rows slot and slot + K -- the newest row of the current window -- and length[b] = 1.  The
+ *   other lanes are not touched and the ring does not advance.
+ * rex_hist_window copies out[b][k] = frames[b][slot + 1 + k], slot being that of the most recent push: for callers that need a
+ *   contiguous tensor or a fixed address.
+ * rex_hist_init: frames <- 0, length <- 0.
+ * Everything is a pure copy: the bits do not depend on the launch shape.
+ *
+ * REX_ERR_ARG, with nothing launched: a null description, frames, length or obs (out in rex_hist_window); K outside [1, 64]; slot outside
+ * [0, K); with_action with a null action in rex_hist_push; term_out without terminal_obs. */
+typedef struct rex_hist_buffers {
+  float* frames;        /* [B][2K][W] */
+  int32_t* length;      /* [B] */
+  int K;
+  int with_action;
+} rex_hist_buffers;
+int rex_hist_init(rex_t* h, const rex_hist_buffers* buf, void* stream);
+int rex_hist_push(rex_t* h, const rex_hist_buffers* buf, int64_t slot, const float* obs, const void* action, const uint8_t* done /* may be NULL */,
+                  const float* terminal_obs /* may be NULL */, float* term_out /* may be NULL, [B][K][W] */, int rows, void* stream);
+int rex_hist_reset(rex_t* h, const rex_hist_buffers* buf, int64_t slot, const uint8_t* mask /* NULL = all */, const float* obs, int rows,
+                   void* stream);
+int rex_hist_window(rex_t* h, const rex_hist_buffers* buf, int64_t slot, float* out /* [B][K][W] */, void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

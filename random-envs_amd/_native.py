@@ -28,6 +28,7 @@ SYMBOLS = [
     "rex_rbuf_gather_nstep", "rex_rbuf_sample_nstep", "rex_per_sample_nstep",
     "rex_rbuf_gather_seq", "rex_rbuf_sample_seq", "rex_per_sample_seq",
     "rex_rows_enable", "rex_reset_rows", "rex_step_rows",
+    "rex_hist_init", "rex_hist_push", "rex_hist_reset", "rex_hist_window",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -61,6 +62,10 @@ class RexRbufBuffers(ctypes.Structure):
 
 class RexPerBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("priority", "tree", "max_priority")] + [("T", ctypes.c_int64)]
+
+
+class RexHistBuffers(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_void_p), ("length", ctypes.c_void_p), ("K", ctypes.c_int), ("with_action", ctypes.c_int)]
 
 
 class RexError(RuntimeError):
@@ -164,6 +169,11 @@ def lib():
     L.rex_rbuf_gather_seq.argtypes = [vp, rp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rex_rbuf_sample_seq.argtypes = [vp, rp, i64, i64, i64, u64, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rex_per_sample_seq.argtypes = [vp, rp, pp, i64, i64, u64, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    hp = ctypes.POINTER(RexHistBuffers)
+    L.rex_hist_init.argtypes = [vp, hp, vp]
+    L.rex_hist_push.argtypes = [vp, hp, i64, vp, vp, vp, vp, vp, i32, vp]
+    L.rex_hist_reset.argtypes = [vp, hp, i64, vp, vp, i32, vp]
+    L.rex_hist_window.argtypes = [vp, hp, i64, vp, vp]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

@@ -3,13 +3,14 @@
 // The kernels are included from headers by env family -- cartpole_kernels.hpp, planar_kernels.hpp (hopper, half-cheetah, walker2d),
 // humanoid_kernels.hpp -- over dev_state.hpp (what every kernel takes) and device_rng.hpp (the DR block and the Philox streams); the
 // math is planar_engine.hpp / humanoid_engine.hpp / humanoid_pair.hpp (the last also owns the pair kernel's view of the SoA state: load_lane /
-// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp, replay_buffer.hpp and eplog.hpp over
+// store_lane / reset_lane, shared with the host harness), the post-passes vecnorm.hpp, rollout.hpp, replay_buffer.hpp, eplog.hpp and hist.hpp over
 // postpass.hpp (their common block, chunk walk, LDS tile and id guard); priority_replay.hpp draws ids for replay_buffer.hpp's sample launch and
 // nstep_replay.hpp puts a window in front of that launch's rows (one rbuf::SampleParams, one block_rows, one launch_sample here).  Profiling probes
 // live in probes.hpp and are empty in this build.  Which lanes, blocks and kernels a handle runs on is decided in launch_shape.hpp
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.  The exported calls past rex_create /
-// rex_destroy are host code in one header per family, included at the end: abi_env.hpp, abi_norm.hpp, abi_rollout.hpp, abi_eplog.hpp, abi_replay.hpp.
+// rex_destroy are host code in one header per family, included at the end: abi_env.hpp, abi_norm.hpp, abi_rollout.hpp, abi_eplog.hpp, abi_replay.hpp,
+// abi_hist.hpp.
 //
 // Execution model: state is SoA in HBM (qpos[nq][B], qvel[nv][B], xi[dim][B], ...), a workgroup is ONE wavefront of up to 64 lanes, and
 // the launch shape follows the batch (rex_create; choose_launch_shape in launch_shape.hpp).  While the GPU has a SIMD for every wave an environment
@@ -43,6 +44,7 @@
 #include "nstep_replay.hpp"
 #include "seq_replay.hpp"
 #include "eplog.hpp"
+#include "hist.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
 #include "cartpole_kernels.hpp"
@@ -562,3 +564,4 @@ static int move_lanes(bool get, T* mine, T* user, long long n, hipStream_t st) {
 #include "abi_rollout.hpp"
 #include "abi_eplog.hpp"
 #include "abi_replay.hpp"
+#include "abi_hist.hpp"
