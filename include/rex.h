@@ -670,6 +670,77 @@ int rex_hist_reset(rex_t* h, const rex_hist_buffers* buf, int64_t slot, const ui
                    void* stream);
 int rex_hist_window(rex_t* h, const rex_hist_buffers* buf, int64_t slot, float* out /* [B][K][W] */, void* stream);
 
+/* ---- automatic domain randomisation: a box over the task that widens and narrows by itself --------------------------------------
+ * Automatic Domain Randomization (OpenAI et al. 2019, "Solving Rubik's Cube with a Robot Hand", Algorithm 1) decides PER EPISODE: an
+ * episode may pin one task dimension to a boundary of the current box, its return lands in that boundary's buffer, a full buffer moves
+ * the boundary, and the next episode is drawn from the moved box.  With auto-reset on the step launch has already restarted the finished
+ * lanes, so on the host this costs a done.nonzero() -- one synchronisation -- per step.  Here it is a post-pass: call order
+ * rex_step -> rex_adr_record (-> rex_eplog_step).  The handle runs with dr_training OFF and auto-reset on; the layer stores the finished
+ * lanes' next task into the handle's xi rows itself.  rex_step and every other family are untouched.  No reference counterpart.
+ *
+ * SETTINGS (rex_adr_config, fixed at enable; d = the handle's task_dim, arrays by task index k < d in rex_get_task's order):
+ *   act[0 .. n_act)  the randomised task indices, strictly increasing, 1 <= n_act <= d.  J = 2 n_act BOUNDARIES: boundary a is dimension
+ *                    act[a >> 1], side a & 1 (0 lower, 1 upper).
+ *   p_b in [0, 1] (f32), m >= 1 (the buffer size), t_lo <= t_hi (f64), delta[k] > 0 on every active k (f32),
+ *   lim_lo[k] <= centre[k] <= lim_hi[k] and the initial box lim_lo <= init_lo <= centre <= init_hi <= lim_hi (f32), seed (u64).
+ * STATE (handle-owned): the box lo[d], hi[d] f32; per boundary a tally n[J] i64, s[J] f64 and the counters expanded[J], shrunk[J],
+ *   held[J] i64; per lane ret f64, len i32, bnd i32 (-1, or the boundary its episode is pinned to), ep u32 (assignments the lane has had);
+ *   scratch: block partials [blocks of 256 lanes][J] and a mask byte per lane.
+ *
+ * rex_adr_record(reward, done, apply): three launches (+ walker2d's derive launch), no synchronisation, no atomics, no host randomness:
+ *   1. TALLY   every lane i: ret[i] += (double)reward[i]; len[i] += 1.  A lane CONTRIBUTES (bnd[i], ret[i]) if done[i] != 0 and bnd[i] >= 0.
+ *              Block b (256 consecutive lanes) writes P[b][a] = (count, sum): the sum is the serial f64 sum of the contributors of boundary a
+ *              in ascending lane order, started from 0.0.
+ *   2. FOLD    for every boundary a, for b ascending with count > 0: n[a] += count; s[a] = s[a] + sum.  Then, if apply != 0 and n[a] >= m:
+ *              mean = s[a] / (double)n[a];
+ *              mean >= t_hi: EXPAND  lower: lo = max(lim_lo, lo - delta)   upper: hi = min(lim_hi, hi + delta)
+ *              mean <= t_lo: SHRINK  lower: lo = min(centre, lo + delta)   upper: hi = max(centre, hi - delta)
+ *              otherwise (a NaN mean included): HOLD.  One of expanded[a] / shrunk[a] / held[a] goes up by one; n[a] = 0, s[a] = 0.0.
+ *   3. ASSIGN  every lane with done[i] != 0 runs assign(i) and sets its mask byte; the others clear theirs.
+ *   4. walker2d: the geometry rows of the masked lanes are re-derived from their new lengths, as rex_set_task does for every lane.
+ * assign(i): e = ep[i]; ep[i] = e + 1.  Philox4x32-10 stream in the map of the other device draws: key = seed ^ 0xD1B54A32D192ED03 (a family
+ *   of its own), subsequence = env_offset + i, offset = 64 e.  u = rocRAND's uniform of a word, in (0, 1].  Word 0 is the coin: a BOUNDARY
+ *   episode iff 1 - u0 < p_b.  Word 1 picks the boundary: a = min((int)((1 - u1) * (float)J), J - 1).  Word 4 + k gives
+ *   xi_k = lo_k + (hi_k - lo_k) * (1 - u_k) for EVERY task index k < d (f32, each operation rounded, nothing fused).  On a boundary
+ *   episode the pinned dimension takes hi (upper) or lo (lower) instead and bnd[i] = a; otherwise bnd[i] = -1.  xi_k goes to the task's row
+ *   of the handle's xi block (the frozen rows of the Unmodeled ids stay untouched).  ret[i] = 0, len[i] = 0.
+ * rex_adr_assign(mask): assign(i) for the lanes with mask[i] != 0 (all when NULL) without a tally -- after rex_reset or a masked reset; a
+ *   boundary episode in progress on such a lane is dropped.  One launch (+ derive).
+ * rex_adr_update: the fold launch with apply = 1 and no partials -- after rex_adr_record(apply = 0) and a merge of the ranks' tallies
+ *   through rex_adr_get_state / rex_adr_set_state, every rank's box then moves identically.
+ * The result depends on the inputs and the call order only: two runs agree bit for bit.
+ *
+ * rex_adr_enable is the only allocating call (rex_destroy frees); it sets the box to init_lo / init_hi, zeroes everything else and
+ *   synchronises, and assigns nothing: call rex_adr_assign(NULL) to start every lane on a task of the box.  Enabling twice, any other
+ *   rex_adr_* call before it, and rex_adr_record while dr_training is on return REX_ERR_STATE; a null pointer, n_act outside [1, d], an
+ *   unsorted or out-of-range act, m < 1, p_b outside [0, 1] or NaN, t_lo > t_hi (or NaN), delta <= 0 on an active dimension and a violated
+ *   limit / centre / box ordering return REX_ERR_ARG.  Nothing is launched or changed on an error. */
+typedef struct rex_adr_config {
+  int32_t n_act;
+  const int32_t* act;          /* [n_act] */
+  float p_b;
+  int64_t m;
+  double t_lo, t_hi;
+  const float* delta;          /* [d]; read on the active dimensions */
+  const float* lim_lo;         /* [d] */
+  const float* lim_hi;         /* [d] */
+  const float* centre;         /* [d] */
+  const float* init_lo;        /* [d] */
+  const float* init_hi;        /* [d] */
+  uint64_t seed;
+} rex_adr_config;
+int rex_adr_enable(rex_t* h, const rex_adr_config* cfg);
+int rex_adr_record(rex_t* h, const float* reward, const uint8_t* done, int apply, void* stream);
+int rex_adr_assign(rex_t* h, const uint8_t* mask /* NULL = all */, void* stream);
+int rex_adr_update(rex_t* h, void* stream);
+/* box, tallies and counters through HOST arrays: lo, hi [d] float; n [J] int64; s [J] double; counters [3][J] int64 (expanded, shrunk,
+ * held).  Synchronises.  set: REX_ERR_ARG for a box outside lim_lo <= lo <= centre <= hi <= lim_hi or a negative count. */
+int rex_adr_get_state(rex_t* h, float* lo, float* hi, int64_t* n, double* s, int64_t* counters);
+int rex_adr_set_state(rex_t* h, const float* lo, const float* hi, const int64_t* n, const double* s, const int64_t* counters);
+/* the per-lane state [dev], stream-ordered: ret (double batch), len (int32 batch), bnd (int32 batch), ep (uint32 batch) */
+int rex_adr_get_lane_state(rex_t* h, double* ret, int32_t* len, int32_t* bnd, uint32_t* ep, void* stream);
+int rex_adr_set_lane_state(rex_t* h, const double* ret, const int32_t* len, const int32_t* bnd, const uint32_t* ep, void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

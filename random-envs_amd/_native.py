@@ -29,6 +29,8 @@ SYMBOLS = [
     "rex_rbuf_gather_seq", "rex_rbuf_sample_seq", "rex_per_sample_seq",
     "rex_rows_enable", "rex_reset_rows", "rex_step_rows",
     "rex_hist_init", "rex_hist_push", "rex_hist_reset", "rex_hist_window",
+    "rex_adr_enable", "rex_adr_record", "rex_adr_assign", "rex_adr_update", "rex_adr_get_state", "rex_adr_set_state",
+    "rex_adr_get_lane_state", "rex_adr_set_lane_state",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -66,6 +68,11 @@ class RexPerBuffers(ctypes.Structure):
 
 class RexHistBuffers(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("length", ctypes.c_void_p), ("K", ctypes.c_int), ("with_action", ctypes.c_int)]
+
+
+class RexAdrConfig(ctypes.Structure):
+    _fields_ = [("n_act", ctypes.c_int32), ("act", ctypes.c_void_p), ("p_b", ctypes.c_float), ("m", ctypes.c_int64), ("t_lo", ctypes.c_double),
+                ("t_hi", ctypes.c_double)] + [(k, ctypes.c_void_p) for k in ("delta", "lim_lo", "lim_hi", "centre", "init_lo", "init_hi")] + [("seed", ctypes.c_uint64)]
 
 
 class RexError(RuntimeError):
@@ -174,6 +181,14 @@ def lib():
     L.rex_hist_push.argtypes = [vp, hp, i64, vp, vp, vp, vp, vp, i32, vp]
     L.rex_hist_reset.argtypes = [vp, hp, i64, vp, vp, i32, vp]
     L.rex_hist_window.argtypes = [vp, hp, i64, vp, vp]
+    L.rex_adr_enable.argtypes = [vp, ctypes.POINTER(RexAdrConfig)]
+    L.rex_adr_record.argtypes = [vp, vp, vp, i32, vp]
+    L.rex_adr_assign.argtypes = [vp, vp, vp]
+    L.rex_adr_update.argtypes = [vp, vp]
+    L.rex_adr_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rex_adr_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rex_adr_get_lane_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rex_adr_set_lane_state.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

@@ -10,7 +10,7 @@
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.  The exported calls past rex_create /
 // rex_destroy are host code in one header per family, included at the end: abi_env.hpp, abi_norm.hpp, abi_rollout.hpp, abi_eplog.hpp, abi_replay.hpp,
-// abi_hist.hpp.
+// abi_hist.hpp, abi_adr.hpp.
 //
 // Execution model: state is SoA in HBM (qpos[nq][B], qvel[nv][B], xi[dim][B], ...), a workgroup is ONE wavefront of up to 64 lanes, and
 // the launch shape follows the batch (rex_create; choose_launch_shape in launch_shape.hpp).  While the GPU has a SIMD for every wave an environment
@@ -45,6 +45,7 @@
 #include "seq_replay.hpp"
 #include "eplog.hpp"
 #include "hist.hpp"
+#include "adr.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
 #include "cartpole_kernels.hpp"
@@ -169,6 +170,10 @@ struct rex_env {
   // terminal obs [obs_dim][B] each; the other kinds' kernels read and write the caller's rows themselves and have none
   float* rows_mem = nullptr;
   int rows_enabled = 0;
+  // rex_adr_* (adr.hpp): one device block allocated by rex_adr_enable -- the box, the boundary tallies and counters, the per-lane state, the
+  // block partials and the mask of the lanes the last assign launch reassigned -- and the launch parameters with the settings in them
+  void* adr_mem = nullptr;
+  adr::Params adr{};
 };
 constexpr size_t EV_POOL = 8192;
 
@@ -530,7 +535,7 @@ extern "C" int rex_destroy(rex_t* h) {
   hipFree(h->dev.qpos); hipFree(h->dev.qvel); hipFree(h->dev.xi); hipFree(h->dev.t); hipFree(h->dev.episode);
   hipFree(h->dev.done); hipFree(h->dev.counters); hipFree(h->d_scratch); hipFree(h->d_chol);
   hipFree(h->dev.geom); hipFree(h->dev.aux); hipFree(h->rp_xi); hipFree(h->rp_rows); hipFree(h->d_map);   // (hipFree(nullptr) is a no-op)
-  hipFree(h->norm_mem); hipFree(h->rollout_mem); hipFree(h->eplog_mem); hipFree(h->rbuf_mem); hipFree(h->per_mem); hipFree(h->rows_mem);
+  hipFree(h->norm_mem); hipFree(h->rollout_mem); hipFree(h->eplog_mem); hipFree(h->rbuf_mem); hipFree(h->per_mem); hipFree(h->rows_mem); hipFree(h->adr_mem);
   for (auto e : h->ev0) hipEventDestroy(e);
   for (auto e : h->ev1) hipEventDestroy(e);
   delete h;
@@ -565,3 +570,4 @@ static int move_lanes(bool get, T* mine, T* user, long long n, hipStream_t st) {
 #include "abi_eplog.hpp"
 #include "abi_replay.hpp"
 #include "abi_hist.hpp"
+#include "abi_adr.hpp"
