@@ -741,6 +741,73 @@ int rex_adr_set_state(rex_t* h, const float* lo, const float* hi, const int64_t*
 int rex_adr_get_lane_state(rex_t* h, double* ret, int32_t* len, int32_t* bnd, uint32_t* ep, void* stream);
 int rex_adr_set_lane_state(rex_t* h, const double* ret, const int32_t* len, const int32_t* bnd, const uint32_t* ep, void* stream);
 
+/* ---- on-device actor: a fused MLP policy, its Gaussian draw, log-probability and value in one launch ------------------------------
+ * What runs BETWEEN two rex_step calls in every on-policy loop: stable-baselines3's default MlpPolicy for continuous actions
+ * (common/policies.py ActorCriticPolicy: mlp_extractor.policy_net / value_net, action_net, value_net, log_std, DiagGaussianDistribution) --
+ * two separate towers of at most three hidden layers, about fifteen eager torch launches.  Here it is ONE launch on `stream`, without an
+ * allocation, a synchronisation or host state, so a captured loop replays.  Inference only: the learner stays in torch ON THE SAME
+ * PARAMETERS (the pointers below are read at every call, so an in-place optimiser step is seen by the next call).  No reference
+ * counterpart.  There is no enable call; the handle contributes B, act_dim, env_offset and the action type and nothing else; rex_step and
+ * every other family are untouched.  Out of scope: categorical heads (a discrete-action handle -- the cart-pole -- returns REX_ERR_STATE),
+ * recurrent cells, squashed-Gaussian actors, a state-dependent std, widths above 64, any backward pass.
+ *
+ * NETWORK (rex_actor_net, a HOST struct of DEVICE pointers, fp32): in_dim in [1, 1024] (not tied to obs_dim: a flattened history window is
+ *   a legal input); activation 0 = tanh, 1 = relu; towers pi and vf, either of which may be NULL -- a null pi computes the value only (the
+ *   bootstrap call on terminal_observation), a null vf computes no value.  A tower has n_hidden in [1, 3] hidden layers of width[l] in
+ *   [1, 64] and a head: layer l < n_hidden is W[l] [width[l]][fan_in] ROW-MAJOR, exactly as nn.Linear.weight stores it (fan_in = in_dim for
+ *   l = 0, width[l - 1] after it) with b[l] [width[l]]; W[n_hidden], b[n_hidden] are the head, [act_dim][width[n_hidden - 1]] for pi and
+ *   [1][...] for vf.  log_std [act_dim] and std [act_dim] = exp(log_std) are BOTH passed in: the device never evaluates exp.  seed keys the draws.
+ * INPUT in [dev]: rows != 0 -- [B][in_dim]; rows == 0 -- [in_dim][B].
+ * ARITHMETIC, per env i, fp32, fully ordered, nothing contracted beyond the fmaf written here (a g++ host build restates it bit for bit):
+ *   layer:   y_j = b_j; for i ascending y_j = fmaf(W[j][i], x_i, y_j); then the activation on the hidden layers, none on the heads.
+ *   relu(x) = fmaxf(x, 0) (so a NaN becomes 0 there, as IEEE maxNum has it).
+ *   tanh32(x), the project's own (csrc/actor.hpp; coefficients from profiles/actor_tanh_fit.py): a NaN returns itself; otherwise it is
+ *     evaluated on a = |x| and the sign of x is copied onto the result, so it is exactly odd.  a < 0.625: fmaf(a * u, P(u), a) with u = a * a
+ *     and P of degree 6 by Horner fmaf; otherwise t = 2 min(a, 10), n = rintf(t * log2 e), r = fmaf(-n, ln2_lo, fmaf(-n, ln2_hi, t)),
+ *     e = Q(r) * 2^n (Q of degree 6 by Horner fmaf, the scaling exact), 1 - 2 / (e + 1) with one IEEE division.  It saturates to +-1 where
+ *     fp32 does.  Error against fp64 tanh over EVERY fp32 in [-10, 10] (the exhaustive sweep of the host build, profiles/actor_tanh_sweep.py):
+ *     at most 1.371 ulp of the result, at x = 0.63022083; T = 1.5 ulp is the bound tests/test_actor_host.py holds a subsample to.
+ *   mean_k (pi head) and value (vf head) by the layer rule.
+ *   eps_k: rocRAND's normal of the Philox4x32-10 stream in the map of the other device draws: key = seed ^ 0xA0761D6478BD642F (a family of
+ *     its own), subsequence = env_offset + i, offset = 32 * draw (mod 2^64); draws in rocrand_normal's pairing (words 2 p, 2 p + 1 give
+ *     eps_2p = .x and eps_(2p+1) = .y).  draw is the caller's call counter, like the draw number of rex_rbuf_sample.
+ *   action_k = fmaf(std_k, eps_k, mean_k);  S = 0, for k ascending S = fmaf(eps_k, eps_k, S);
+ *   s = 0, for k ascending s = s + log_std_k;  c = s + (float)act_dim * 0.91893853f (a product, then a sum);  logp = fmaf(-0.5f, S, -c).
+ *   deterministic != 0: no draw is made, eps = 0, action = mean, logp = -c.
+ *   Actions are NOT clipped: the step kernels clamp ctrl themselves.
+ * OUTPUTS [dev]: action_out [B][act_dim] (rows != 0) or [act_dim][B] (rows == 0); logp_out [B] (may be NULL); value_out [B]; noise_out
+ *   [B][act_dim] (may be NULL) receives eps as drawn (zeros when deterministic).  Outputs of an absent tower are never written.
+ * A non-finite input makes that lane's mean, action and value whatever the arithmetic gives (non-finite under tanh; relu's fmaxf drops a NaN)
+ *   -- logp is a function of the noise and log_std alone -- and touches no other lane.  Under relu a NaN input therefore leaves the lane
+ *   FINITE: every first-layer unit it reaches becomes fmaxf(NaN, 0) = 0 (an inf input stays visible unless its weights cancel).  The tests pin
+ *   both activations; a caller that must see a non-finite observation tests the observation.  The bits
+ *   do not depend on the launch shape, on rows, or on how the batch is sharded over handles (env_offset).
+ *
+ * Checks, in this order, nothing launched on a failure: null handle (REX_ERR_ARG); a discrete-action handle (REX_ERR_STATE); then
+ *   REX_ERR_ARG for: a null net; both towers null; in_dim outside [1, 1024]; an activation other than 0 / 1; per present tower, pi first:
+ *   n_hidden outside [1, 3], a width outside [1, 64], a null W or b of a layer or of the head; pi without log_std, std or action_out; vf
+ *   without value_out; a negative draw; a null input; then REX_ERR_UNSUPPORTED for a handle whose act_dim is above 32, the
+ *   number of action rows the kernel's epilogue is built for (no env kind has more than 17); and last REX_ERR_ARG for a batch of more than
+ *   2^31 - 1 waves of 64 envs, which one launch does not take. */
+#define REX_ACTOR_MAX_HIDDEN 3
+typedef struct rex_actor_tower {
+  int n_hidden;
+  int width[REX_ACTOR_MAX_HIDDEN];
+  const float* W[REX_ACTOR_MAX_HIDDEN + 1];   /* [dev] hidden layers, then the head at index n_hidden */
+  const float* b[REX_ACTOR_MAX_HIDDEN + 1];
+} rex_actor_tower;
+typedef struct rex_actor_net {
+  int in_dim;
+  int activation;                /* 0 tanh, 1 relu */
+  const rex_actor_tower* pi;     /* [host], may be NULL */
+  const rex_actor_tower* vf;     /* [host], may be NULL */
+  const float* log_std;          /* [dev, act_dim] */
+  const float* std;              /* [dev, act_dim] */
+  uint64_t seed;
+} rex_actor_net;
+int rex_actor_act(rex_t* h, const rex_actor_net* net, const float* in, int rows, int64_t draw, int deterministic, float* action_out,
+                  float* logp_out /* may be NULL */, float* value_out, float* noise_out /* may be NULL */, void* stream);
+
 const char* rex_last_error(void);
 const char* rex_version(void);
 

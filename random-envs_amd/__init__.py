@@ -16,6 +16,7 @@ from .prioritized_replay import PrioritizedReplayBuffer  # noqa: F401
 from .episode_log import EpisodeLog, merge_logs  # noqa: F401
 from .history import HistoryStack  # noqa: F401
 from .adr import AutoDR, merge_tallies  # noqa: F401
+from .actor import DeviceActor  # noqa: F401
 from . import _native  # noqa: F401
 
-__all__ = ["make", "registered_ids", "spec", "VecRandomEnv", "NormalizedVecRandomEnv", "merge_stats", "RolloutBuffer", "ReplayBuffer", "PrioritizedReplayBuffer", "EpisodeLog", "merge_logs", "HistoryStack", "AutoDR", "merge_tallies"]
+__all__ = ["make", "registered_ids", "spec", "VecRandomEnv", "NormalizedVecRandomEnv", "merge_stats", "RolloutBuffer", "ReplayBuffer", "PrioritizedReplayBuffer", "EpisodeLog", "merge_logs", "HistoryStack", "AutoDR", "merge_tallies", "DeviceActor"]

@@ -31,6 +31,7 @@ SYMBOLS = [
     "rex_hist_init", "rex_hist_push", "rex_hist_reset", "rex_hist_window",
     "rex_adr_enable", "rex_adr_record", "rex_adr_assign", "rex_adr_update", "rex_adr_get_state", "rex_adr_set_state",
     "rex_adr_get_lane_state", "rex_adr_set_lane_state",
+    "rex_actor_act",
 ]
 
 ENV_KINDS = {"cartpole": 0, "hopper": 1, "halfcheetah": 2, "walker2d": 3, "humanoid": 4}
@@ -73,6 +74,19 @@ class RexHistBuffers(ctypes.Structure):
 class RexAdrConfig(ctypes.Structure):
     _fields_ = [("n_act", ctypes.c_int32), ("act", ctypes.c_void_p), ("p_b", ctypes.c_float), ("m", ctypes.c_int64), ("t_lo", ctypes.c_double),
                 ("t_hi", ctypes.c_double)] + [(k, ctypes.c_void_p) for k in ("delta", "lim_lo", "lim_hi", "centre", "init_lo", "init_hi")] + [("seed", ctypes.c_uint64)]
+
+
+ACTOR_MAX_HIDDEN = 3
+
+
+class RexActorTower(ctypes.Structure):
+    _fields_ = [("n_hidden", ctypes.c_int), ("width", ctypes.c_int * ACTOR_MAX_HIDDEN), ("W", ctypes.c_void_p * (ACTOR_MAX_HIDDEN + 1)),
+                ("b", ctypes.c_void_p * (ACTOR_MAX_HIDDEN + 1))]
+
+
+class RexActorNet(ctypes.Structure):
+    _fields_ = [("in_dim", ctypes.c_int), ("activation", ctypes.c_int), ("pi", ctypes.POINTER(RexActorTower)), ("vf", ctypes.POINTER(RexActorTower)),
+                ("log_std", ctypes.c_void_p), ("std", ctypes.c_void_p), ("seed", ctypes.c_uint64)]
 
 
 class RexError(RuntimeError):
@@ -189,6 +203,7 @@ def lib():
     L.rex_adr_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rex_adr_get_lane_state.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rex_adr_set_lane_state.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rex_actor_act.argtypes = [vp, ctypes.POINTER(RexActorNet), vp, i32, i64, i32, vp, vp, vp, vp, vp]
     L.rex_last_error.restype = ctypes.c_char_p
     L.rex_version.restype = ctypes.c_char_p
     _lib = L

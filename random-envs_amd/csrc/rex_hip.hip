@@ -10,7 +10,7 @@
 // (pure host functions, tested without a GPU); the handle keeps the result as one LaunchShape.  Everything that differs by env kind
 // goes through ONE dispatch, with_kind, which is also the only place that asks which kinds this build compiles.  The exported calls past rex_create /
 // rex_destroy are host code in one header per family, included at the end: abi_env.hpp, abi_norm.hpp, abi_rollout.hpp, abi_eplog.hpp, abi_replay.hpp,
-// abi_hist.hpp, abi_adr.hpp.
+// abi_hist.hpp, abi_adr.hpp, abi_actor.hpp (the on-device actor, actor.hpp: one launch of its own, no handle state).
 //
 // Execution model: state is SoA in HBM (qpos[nq][B], qvel[nv][B], xi[dim][B], ...), a workgroup is ONE wavefront of up to 64 lanes, and
 // the launch shape follows the batch (rex_create; choose_launch_shape in launch_shape.hpp).  While the GPU has a SIMD for every wave an environment
@@ -46,6 +46,7 @@
 #include "eplog.hpp"
 #include "hist.hpp"
 #include "adr.hpp"
+#include "actor.hpp"
 #include "dev_state.hpp"
 #include "device_rng.hpp"
 #include "cartpole_kernels.hpp"
@@ -571,3 +572,4 @@ static int move_lanes(bool get, T* mine, T* user, long long n, hipStream_t st) {
 #include "abi_replay.hpp"
 #include "abi_hist.hpp"
 #include "abi_adr.hpp"
+#include "abi_actor.hpp"
